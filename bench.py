@@ -15,7 +15,10 @@ ncclAllReduce of the per-GPU films at the end, inside the timed region).  Launch
     (bring-up, reported as `oversubscribed`).
 Every form refuses (exit code 2) to run with fewer than N visible devices: never a silently smaller job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (every N) and, at N = 1, `cpu_baseline`, `equal_time_rmse`, `configs`."""
+Prints ONE JSON line on rank 0 with `roofline` from the timed window's own HIP events (every N).  A plain run
+does only what that line's headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and the line.  Everything measured
+on top -- at N = 1 `cpu_baseline`, `equal_time_rmse`, the `configs` array and `roofline.standalone`; at N > 1 the veach-door line -- runs with
+--full only (--no-cpu-baseline / --no-rmse / --no-configs leave parts of it out)."""
 import argparse
 import importlib
 import json
@@ -38,7 +41,7 @@ def parse():
     ap.add_argument("--chains", type=int, default=1 << 20, help="chains per GPU (default 2^20)")
     ap.add_argument("--init-samples", type=int, default=0, help="MLT init samples (default 8 * total chains)")
     ap.add_argument("--init-threads", type=int, default=65536)
-    ap.add_argument("--samples-per-chain", type=int, default=256)
+    ap.add_argument("--samples-per-chain", type=int, default=None, help="mutations per chain (default max(256, warmup + steps): every timed step moves every chain)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time bound of the CPU baseline sample")
     ap.add_argument("--no-rmse", action="store_true")
@@ -48,7 +51,11 @@ def parse():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, the driver's form): --chains per GPU, the job grows with N; strong: --chains is the job's TOTAL, split evenly over the N GPUs (the other reading of north_star's '>= 6x at 8 GPUs')")
     ap.add_argument("--in-process", action="store_true", help="--gpus N > 1 without a launcher: ONE process drives N contexts (device copies instead of RCCL); the default is one process per GPU over RCCL")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline: CPU baseline, equal-time RMSE, the other workloads (`configs`), the standalone roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed (film, a fixed sample of the chain states, counters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.samples_per_chain is None:
+        args.samples_per_chain = max(256, args.warmup + args.steps)
     if args.scaling == "strong":  # everything below works with chains PER GPU
         if args.chains % args.gpus:
             ap.error("--scaling strong: --chains (the job's total) must be a multiple of --gpus")
@@ -375,12 +382,32 @@ def pmc_traffic_meta():
         return None
 
 
+DUMP_CHAINS = 1 << 16
+STAT_KEYS = ("steps", "largeSteps", "accepted", "gradCalls", "cacheQueries", "cacheHits", "resets", "cacheReadyMask", "weightSum")
+
+
+def dump_outputs(directory, ren, normalization):
+    """--dump-outputs: what the timed steps leave a caller of the path, as float32 / float64 .npy files -- the film (every splat up to the last
+    step), the current states (lmc_chain_summary rows) of a fixed sample of DUMP_CHAINS chains drawn with seed 0 and their chain indices, and
+    the step counters + splat-weight sum + the MLTInit normalization.  The inputs are the same from run to run (seed offset 0, fixed sizes)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    summ = ren.summary(0)
+    ids = np.sort(np.random.default_rng(0).choice(len(summ), min(len(summ), DUMP_CHAINS), replace=False))
+    st = ren.stats()
+    np.save(os.path.join(directory, "film.npy"), ren.film().astype(np.float32))
+    np.save(os.path.join(directory, "chain_states.npy"), summ[ids].astype(np.float32))
+    np.save(os.path.join(directory, "chain_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(directory, "stats.npy"), np.array([st[k] for k in STAT_KEYS] + [normalization], np.float64))
+
+
 def die(msg, code=2):
     sys.stderr.write("bench.py: " + msg + "\n")
     sys.exit(code)
 
 
-def inprocess_job(args, p, gc, name, xml, kw, devices, warm, steps, algo_bytes):
+def inprocess_job(args, p, gc, name, xml, kw, devices, warm, steps, algo_bytes, dump=None):
     """One workload on len(devices) GPUs driven from THIS process (`--in-process`): one context per device, joined into an in-process job (sharded
     MLTInit, contiguous chain ranges, per-step exchange of the cache pushes while the gradient caches fill, one film merge at the end); a host thread
     per member queues its launches.  Timed like the single-GPU line: `warm` untimed steps, then `steps` steps + the film merge bracketed by syncs
@@ -407,6 +434,8 @@ def inprocess_job(args, p, gc, name, xml, kw, devices, warm, steps, algo_bytes):
     for r in rens:
         r.sync()
     dt = time.time() - t0
+    if dump:
+        dump_outputs(dump, rens[0], norm)  # the merged film; the chain states of the first member's range
     per_rank, fracs, dom_ms_r, dom_names, issue = [], [], [], [], []
     s1 = [r.stats() for r in rens]
     for r, kk0, ss0, ss1 in zip(rens, k0, s0, s1):
@@ -452,7 +481,7 @@ def main_inprocess(args):
             die("--gpus %d but only %d HIP device(s) visible to this process: refusing to measure a smaller job under that name" % (args.gpus, have))
     door = os.path.join(ROOT, "scenes", "veachdoor", "lmc.xml")
     head = inprocess_job(args, p, gc, "torus scene, %d persistent chains per GPU, Lambertian-only BSDF, max path length 6 (BASELINE.json configs[1])" % args.chains,
-                         gc.TORUS, dict(force_diffuse=1, max_depth=6), devices, args.warmup, args.steps, ALGO_BYTES_PER_STEP)
+                         gc.TORUS, dict(force_diffuse=1, max_depth=6), devices, args.warmup, args.steps, ALGO_BYTES_PER_STEP, args.dump_outputs)
     out = {
         "metric": "MALA chain-steps/sec, torus scene", "value": head["value"], "unit": "chain-steps/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
@@ -465,7 +494,7 @@ def main_inprocess(args):
         "multi_gpu": {k: head[k] for k in ("per_rank_step_ms", "per_rank_step_ms_spread", "host_issue_ms_per_step_per_rank", "group", "film_merge_ms", "init_seconds", "accept_rate", "film_sum")},
         "lmc_env": lmc_env(),
     }
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         try:  # north_star names both scenes: the veach-door LMC workload as a second multi-GPU line
             out["configs"] = [inprocess_job(args, p, gc, "veach-door, shipped lmc.xml, LMC (BASELINE.json configs[3]), chains sharded over the GPUs", door, {}, devices, 40, 40, algorithmic_bytes(8))]
         except Exception as e:  # noqa: BLE001 -- the headline line must still come out
@@ -549,7 +578,7 @@ class TorchBoot:
         self.dist.destroy_process_group()
 
 
-def rank_job(args, p, gc, boot, rank, world, local, name, xml, kw, warm, steps, algo_bytes, kernel_name, standalone_ok):
+def rank_job(args, p, gc, boot, rank, world, local, name, xml, kw, warm, steps, algo_bytes, kernel_name, standalone_ok, dump=None):
     """One workload on this rank's GPU as rank `rank` of a `world`-rank job: scene, communicator (world > 1: RCCL inside the library, its id over
     `boot`), sharded MLTInit, `warm` untimed steps, then EXACTLY `steps` steps + the film all-reduce bracketed by a barrier + stream sync on
     both sides; the time is the MAX over the ranks.  Returns the job's figures on every rank (per-rank lists gathered through the communicator)."""
@@ -588,6 +617,8 @@ def rank_job(args, p, gc, boot, rank, world, local, name, xml, kw, warm, steps, 
     dt = time.time() - t0
     if multi:
         dt = ren.comm_allreduce([dt], "max")[0]
+    if dump and rank == 0:
+        dump_outputs(dump, ren, norm)
     kernel_ms, launches = ren.step_timing()
     k1 = ren.kernel_timing_split()
     issue_ms, issue_steps = ren.host_issue_timing()
@@ -713,9 +744,10 @@ def main_rank(args):
     multi = world > 1 or bool(os.environ.get("LMC_BENCH_FORCE_DIST"))
     head_name = "torus scene, %d persistent chains per GPU, Lambertian-only BSDF, max path length 6 (BASELINE.json configs[1])" % args.chains
     head = rank_job(args, p, gc, boot, rank, world, local, head_name, gc.TORUS, dict(force_diffuse=1, max_depth=6), args.warmup, args.steps, ALGO_BYTES_PER_STEP,
-                    "k_step_small<true, false, false, true, true> (rocprofv3's name: LDS stack, Lambertian, no region profiling, no light sub-paths, quantised nodes; plain small steps of a scene lit by its environment map alone)", True)
+                    "k_step_small<true, false, false, true, true> (rocprofv3's name: LDS stack, Lambertian, no region profiling, no light sub-paths, quantised nodes; plain small steps of a scene lit by its environment map alone)",
+                    args.full, args.dump_outputs)
     door = None
-    if multi and not args.no_configs:  # north_star names both scenes at 1 / 2 / 4 / 8 GPUs: the veach-door LMC workload as the job's second line
+    if multi and args.full and not args.no_configs:  # north_star names both scenes at 1 / 2 / 4 / 8 GPUs: the veach-door LMC workload as the job's second line
         try:
             door = rank_job(args, p, gc, boot, rank, world, local, "veach-door, shipped lmc.xml (area light, textures, max path length 8), LMC (BASELINE.json configs[3]), chains sharded over the GPUs",
                             os.path.join(ROOT, "scenes", "veachdoor", "lmc.xml"), {}, 40, 40, algorithmic_bytes(8), "k_step_small<glossy> (plain small steps)", False)
@@ -784,9 +816,9 @@ def main_rank(args):
             out["multi_gpu"] = head["multi_gpu"]
             if door is not None:
                 out["configs"] = [door]
-        if not args.no_configs and not multi:
+        if args.full and not args.no_configs and not multi:
             out["configs"] = other_configs(args, p, gc)
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
             except Exception as e:  # the bench line must still come out

@@ -20,7 +20,7 @@ run() {
   local v="$1"
   [ "$v" = "-" ] && v="LMC_X=default"
   echo "== $v" >&2
-  env $v timeout 300 python bench.py --no-cpu-baseline --no-rmse --no-configs --steps $STEPS --warmup $WARM $EXTRA 2>/dev/null | tail -1 | VARIANT="$v" python -c "
+  env $v timeout 300 python bench.py --full --no-cpu-baseline --no-rmse --no-configs --steps $STEPS --warmup $WARM $EXTRA 2>/dev/null | tail -1 | VARIANT="$v" python -c "
 import json,os,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']

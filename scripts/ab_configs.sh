@@ -5,7 +5,7 @@ OUT=$1; shift; [ "$1" = "--" ] && shift
 run() {
   local v="$1"; [ "$v" = "-" ] && v="LMC_X=default"
   echo "== $v" >&2
-  env $v timeout 600 python bench.py --no-cpu-baseline --no-rmse --steps 48 --warmup 40 2>/dev/null | tail -1 | VARIANT="$v" python -c "
+  env $v timeout 600 python bench.py --full --no-cpu-baseline --no-rmse --steps 48 --warmup 40 2>/dev/null | tail -1 | VARIANT="$v" python -c "
 import json,os,sys
 d=json.loads(sys.stdin.read())
 row={'variant': os.environ['VARIANT'], 'headline': {'value': d['value'], 'ms_per_step': d['ms_per_step'], 'k_step_small_ms': d['step_ms']['k_step_small'], 'large_and_generic_ms': d['step_ms']['large_and_generic'], 'standalone_ms': d['roofline'].get('standalone', {}).get('avg_launch_ms')}}

@@ -5,16 +5,16 @@ OUT=$(realpath -m "$1"); mkdir -p "$OUT"
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd "$ROOT"
 timeout 1500 python -m pytest tests -m gpu -q > "$OUT/pytest_gpu.txt" 2>&1; tail -3 "$OUT/pytest_gpu.txt"
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 2>"$OUT/bench_driver.err" | tail -1 > "$OUT/bench_steps20_warmup5.json"
-timeout 400 python bench.py 2>"$OUT/bench_default.err" | tail -1 > "$OUT/bench_default.json"
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 2>"$OUT/bench_driver.err" | tail -1 > "$OUT/bench_steps20_warmup5.json"
+timeout 400 python bench.py --full 2>"$OUT/bench_default.err" | tail -1 > "$OUT/bench_default.json"
 # a complete run: every chain's 256 mutations from a fresh start (cache fill at the beginning, draining chains at the end)
-timeout 400 python bench.py --steps 256 --warmup 0 --no-cpu-baseline --no-rmse --no-configs 2>/dev/null | tail -1 > "$OUT/bench_full_run_256_steps.json"
+timeout 400 python bench.py --full --steps 256 --warmup 0 --no-cpu-baseline --no-rmse --no-configs 2>/dev/null | tail -1 > "$OUT/bench_full_run_256_steps.json"
 # --gpus N without N devices: refused (exit code 2, message on stderr, no JSON line); the in-process job itself with the bring-up switch
 python bench.py --gpus 2 --chains 65536 --steps 8 --warmup 4 > "$OUT/bench_gpus2_refused.out" 2> "$OUT/bench_gpus2_refused.err"; echo "exit code $?" >> "$OUT/bench_gpus2_refused.err"
-LMC_BENCH_OVERSUBSCRIBE=1 timeout 400 python bench.py --gpus 2 --in-process --chains 262144 --steps 20 --warmup 30 2>/dev/null | tail -1 > "$OUT/bench_inprocess_2_ranks_one_device.json"
-( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kstats && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -- python "$ROOT/bench.py" --no-cpu-baseline --no-rmse > "$OUT/rocprof_bench.log" 2>&1
+LMC_BENCH_OVERSUBSCRIBE=1 timeout 400 python bench.py --full --gpus 2 --in-process --chains 262144 --steps 20 --warmup 30 2>/dev/null | tail -1 > "$OUT/bench_inprocess_2_ranks_one_device.json"
+( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kstats && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-rmse > "$OUT/rocprof_bench.log" 2>&1
   f=$(find /tmp/kstats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv" )
-( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kstats2 && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats2 -- python "$ROOT/bench.py" --no-cpu-baseline --no-rmse --steps 20 --warmup 5 > "$OUT/rocprof_bench_driver.log" 2>&1
+( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kstats2 && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats2 -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-rmse --steps 20 --warmup 5 > "$OUT/rocprof_bench_driver.log" 2>&1
   f=$(find /tmp/kstats2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_steps20_warmup5.csv" )
 timeout 1500 bash scripts/pmc_passes.sh "$OUT/pmc" --no-rmse --no-configs > "$OUT/pmc.log" 2>&1
 rm -rf "$OUT"/pmc/pass*/ "$OUT"/pmc/calib_*/   # keep the summaries, drop the raw csv trees

@@ -23,7 +23,7 @@ for v in "$@"; do
   i=0
   for grp in "${GROUPS_[@]}"; do
     i=$((i+1))
-    ( cd "$REPO" && env $vv timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$TMP/run/pass$i" -- python bench.py --no-cpu-baseline --no-rmse --no-configs --steps 32 --warmup 40 > "$TMP/run/pass$i.log" 2>&1 )
+    ( cd "$REPO" && env $vv timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$TMP/run/pass$i" -- python bench.py --full --no-cpu-baseline --no-rmse --no-configs --steps 32 --warmup 40 > "$TMP/run/pass$i.log" 2>&1 )
   done
   python "$REPO/scripts/pmc_summary.py" "$TMP/run" > "$TMP/run/summary.json"
   VARIANT="$vv" python - "$TMP/run/summary.json" "$TMP/run/pass1.log" <<'PY' | tee -a "$OUT"

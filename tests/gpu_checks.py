@@ -241,43 +241,119 @@ def trig_cases(seed=2, n=1 << 20):
     ]
 
 
+REF_RUNS = os.path.join(ROOT, "tests", "golden", "ref_runs")
+
+
+def oracle_run_config(width, height, num_init, n_chains, init_threads, per_chain, steps, max_depth=6, scene=TORUS, mala=True, opts=None, force_diffuse=1):
+    """The arguments that fix an oracle run of run_pair (everything but the gradient library); the scene as a path relative to the repository"""
+    return dict(width=width, height=height, num_init=num_init, n_chains=n_chains, init_threads=init_threads, per_chain=per_chain, steps=steps, max_depth=max_depth,
+                scene=os.path.relpath(scene, ROOT), mala=bool(mala), opts=sorted((k, float(v)) for k, v in (opts or {}).items()), force_diffuse=force_diffuse)
+
+
+def oracle_run(cfg, glib):
+    """The oracle side of run_pair: MLTInit, then `steps` lock-step mutations; the figures run_pair compares with the GPU's"""
+    L = oracle_lib()
+    orc = _orc.Oracle(L, os.path.join(ROOT, cfg["scene"]), cfg["force_diffuse"], cfg["max_depth"], cfg["width"], cfg["height"], 0, glib)
+    for k, v in cfg["opts"]:
+        L.orc_set_option(orc.h, k.encode(), float(v))
+    if not cfg["mala"]:
+        L.orc_set_option(orc.h, b"mala", 0.0)
+    on, oc = orc.init(cfg["num_init"], cfg["n_chains"], cfg["init_threads"])
+    si = orc.summary(1)
+    orc.setup_chains(cfg["per_chain"], 0)
+    orc.step(cfg["steps"])
+    out = dict(norm=on, contribs=oc, init_summary=si, stats=orc.stats(), film=orc.film(), summary=orc.summary(0))
+    orc.close()
+    return out
+
+
+def ref_run_path(cfg):
+    import hashlib
+    import json
+
+    return os.path.join(REF_RUNS, "run_%s.npz" % hashlib.sha256(json.dumps(cfg, sort_keys=True).encode()).hexdigest()[:16])
+
+
+STAT_KEYS = ("steps", "largeSteps", "accepted", "gradCalls", "cacheQueries", "cacheHits", "resets", "cacheReadyMask")
+
+
+def save_ref_run(cfg, run):
+    import json
+
+    os.makedirs(REF_RUNS, exist_ok=True)
+    np.savez_compressed(ref_run_path(cfg), config=np.array(json.dumps(cfg, sort_keys=True)), norm=np.float64(run["norm"]), contribs=np.int64(run["contribs"]),
+                        stats=np.array([run["stats"][k] for k in STAT_KEYS], np.int64), weight_sum=np.float64(run["stats"]["weightSum"]),
+                        init_summary=run["init_summary"], film=run["film"], summary=run["summary"])
+
+
+def load_ref_run(cfg):
+    """A recorded oracle run with the reference's derivative programs (tests/golden/make_golden_ref_runs.py)"""
+    path = ref_run_path(cfg)
+    if not os.path.exists(path):
+        raise FileNotFoundError("no recorded oracle run for %r (%s): regenerate with tests/golden/make_golden_ref_runs.py" % (cfg, os.path.relpath(path, ROOT)))
+    d = np.load(path)
+    stats = dict(zip(STAT_KEYS, (int(x) for x in d["stats"])))
+    stats["weightSum"] = float(d["weight_sum"])
+    return dict(norm=float(d["norm"]), contribs=int(d["contribs"]), init_summary=d["init_summary"], stats=stats, film=d["film"], summary=d["summary"])
+
+
+def emitter_end_states(orc, si):
+    """Init states of an oracle whose camera path (no light sub-path, c >= 4) ends on an area light, every len // 60-th of them:
+    ([(i, c, l, primary, vert)], how many there are in all)"""
+    emit = []
+    for i in np.nonzero((si[:, 2] == 0) & (si[:, 1] >= 4))[0]:
+        c, l, prim, vert = orc.serialize_init_state(int(i))
+        if vert[3 + 59 * (c - 2) + 46] == 1.0:  # the path's last vertex carries an area light slot
+            emit.append((int(i), c, l, prim, vert))
+    return emit[:: max(1, len(emit) // 60)], len(emit)
+
+
+def ref_evals(name, orc, states):
+    """(log-luminance, gradient) of the reference's generated programs on the oracle's serialised states [(i, c, l, primary, vert)]; where the
+    programs are not built, as recorded for the same states (tests/golden/ref_runs/ref_eval_<name>.npz, tests/golden/make_golden_ref_runs.py)"""
+    if pathref():
+        return [orc.ref_eval(c, l, prim, vert) for _, c, l, prim, vert in states]
+    path = os.path.join(REF_RUNS, "ref_eval_%s.npz" % name)
+    d = np.load(path)
+    assert np.array_equal(d["index"], [s[0] for s in states]), "the recorded states of %s are not these: regenerate with tests/golden/make_golden_ref_runs.py" % path
+    return [(float(ll), g[: 2 * max(c + l - 1, 2)].copy()) for ll, g, (_, c, l, _, _) in zip(d["loglum"], d["grad"], states)]
+
+
 def run_pair(width, height, num_init, n_chains, init_threads, per_chain, steps, use_gradient, max_depth=6, scene=TORUS, mala=True, opts=None,
              force_diffuse=1, oracle_grad="reference"):
     """Runs the same configuration on the oracle and on the GPU; returns a dict of comparison figures.
-    oracle_grad: "reference" = the reference's generated derivative programs (oracle/_ref), "product" = the product's
-    path program compiled for the host (tests/helpers)."""
+    oracle_grad: "reference" = the reference's generated derivative programs (oracle/_ref; where they are not built, the oracle's figures of
+    that run as recorded under tests/golden/ref_runs), "product" = the product's path program compiled for the host (tests/helpers)."""
     p = pkg()
-    L = oracle_lib()
-    glib = (pathref() if oracle_grad == "reference" else host_pathfunc_lib()) if use_gradient else ""
-    orc = _orc.Oracle(L, scene, force_diffuse, max_depth, width, height, 0, glib)
+    cfg = oracle_run_config(width, height, num_init, n_chains, init_threads, per_chain, steps, max_depth, scene, mala, opts, force_diffuse)
+    if use_gradient and oracle_grad == "reference" and not pathref():
+        o = load_ref_run(cfg)
+    else:
+        o = oracle_run(cfg, (pathref() if oracle_grad == "reference" else host_pathfunc_lib()) if use_gradient else "")
     ren = p.Renderer(scene, force_diffuse=force_diffuse, max_depth=max_depth, width=width, height=height, seed_offset=0, use_gradient=use_gradient)
     for k, v in (opts or {}).items():
-        L.orc_set_option(orc.h, k.encode(), float(v))
         ren.set_option(k, v)
     if not mala:
-        L.orc_set_option(orc.h, b"mala", 0.0)
         ren.set_option("mala", 0)
-    on, oc = orc.init(num_init, n_chains, init_threads)
+    on, oc = o["norm"], o["contribs"]
     gn, gc = ren.init_chains(num_init, n_chains, init_threads, per_chain)
-    si, gi = orc.summary(1), ren.summary(1)
+    si, gi = o["init_summary"], ren.summary(1)
     res = dict(norm_oracle=on, norm_gpu=gn, contribs_oracle=oc, contribs_gpu=gc)
     same_cl = (si[:, 1] == gi[:, 1]) & (si[:, 2] == gi[:, 2])
     res["init_cl_match"] = float(same_cl.mean())
     ok = same_cl & (si[:, 3] > 0)
     res["init_ls_relerr_max"] = float(np.max(np.abs(si[ok, 3] - gi[ok, 3]) / si[ok, 3])) if ok.any() else 0.0
     res["init_pss_maxdiff"] = float(np.max(np.abs(si[ok, 16:] - gi[ok, 16:]))) if ok.any() else 0.0
-    orc.setup_chains(per_chain, 0)
-    orc.step(steps)
     ren.step(steps)
-    so, sg = orc.stats(), ren.stats()
+    so, sg = o["stats"], ren.stats()
     res["stats_oracle"], res["stats_gpu"] = so, sg
-    fo, fg = orc.film(), ren.film()
+    fo, fg = o["film"], ren.film()
     lo, lg = lum(fo), lum(fg)
     res["film_sum_oracle"], res["film_sum_gpu"] = float(lo.sum()), float(lg.sum())
     res["film_rel_l2"] = float(np.linalg.norm(lo - lg) / max(np.linalg.norm(lo), 1e-30))
     res["energy_gpu"] = float(lg.sum() / (gn * sg["weightSum"])) if sg["weightSum"] > 0 else 0.0
     res["energy_oracle"] = float(lo.sum() / (on * so["weightSum"])) if so["weightSum"] > 0 else 0.0
-    co, cg = orc.summary(0), ren.summary(0)
+    co, cg = o["summary"], ren.summary(0)
     same = (co[:, 0] == cg[:, 0]) & (co[:, 1] == cg[:, 1]) & (co[:, 2] == cg[:, 2])
     close = same & (np.abs(co[:, 3] - cg[:, 3]) <= 1e-3 * np.abs(co[:, 3]) + 1e-12)
     res["final_state_match"] = float(close.mean())
@@ -286,7 +362,6 @@ def run_pair(width, height, num_init, n_chains, init_threads, per_chain, steps, 
         keys, cnt = np.unique((cs[:, 1] * 16 + cs[:, 2]).astype(int), return_counts=True)
         res[name] = {int(k): float(v) / len(cs) for k, v in zip(keys, cnt)}
     res["nonfinite_gpu"] = int((~np.isfinite(fg)).sum())
-    orc.close()
     ren.close()
     return res
 

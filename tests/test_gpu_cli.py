@@ -72,7 +72,7 @@ def test_bench_multi_rank_code_path_with_one_rank():
 
     env = dict(os.environ, LMC_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29517",
-           os.path.join(gc.ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--chains", "65536", "--no-cpu-baseline", "--no-rmse"]
+           os.path.join(gc.ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--chains", "65536", "--full", "--no-cpu-baseline", "--no-rmse"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=gc.ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

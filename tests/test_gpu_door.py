@@ -218,17 +218,11 @@ def test_door_light_coordinate_sampling():
         # one state of 8192 sits on an ill-conditioned path (2e-4 relative, 1.5e-3 in one pss entry): scripts/debug/arealight_state_diff.py
         assert np.allclose(si[:, 3], gi[:, 3], rtol=1e-3) and np.allclose(si[:, 4], gi[:, 4], rtol=1e-3)
         assert (np.abs(si[:, 3] / gi[:, 3] - 1) > 1e-5).sum() <= 8 and (np.abs(si[:, 16:] - gi[:, 16:]).max(axis=1) > 1e-5).sum() <= 8
-        emit = []
-        for i in np.nonzero((si[:, 2] == 0) & (si[:, 1] >= 4))[0]:
-            c, l, prim, vert = orc.serialize_init_state(int(i))
-            if vert[3 + 59 * (c - 2) + 46] == 1.0:  # the path's last vertex carries an area light slot
-                emit.append((int(i), c, l, prim, vert))
-        assert len(emit) >= 1000, len(emit)
-        emit = emit[:: max(1, len(emit) // 60)]
+        emit, n_emit = gc.emitter_end_states(orc, si)
+        assert n_emit >= 1000, n_emit
         if flag:
-            for i, c, l, prim, vert in emit:
+            for (i, c, l, prim, vert), (rll, rg) in zip(emit, gc.ref_evals("lightcoord_arealight", orc, emit)):
                 ll, g = p.grad_batch(c, l, prim[: 2 * (c + l - 1) + 1, None].copy(), sp, vert[: 238 + 59 * (c + l - 3), None].copy())
-                rll, rg = orc.ref_eval(c, l, prim, vert)
                 assert abs(ll[0] - rll) < 2e-3 and np.linalg.norm(rg - g[:, 0]) <= 1e-2 * max(np.linalg.norm(rg), 1e-2), (i, c, l)
         emitter_ss[flag] = {i: (float(si[i, 4]), si[i, 16:].copy()) for i, *_ in emit}
         orc.close()

@@ -18,7 +18,7 @@ def _run(relocate, mala, n_chains, steps, opts, checkpoints=(), max_depth=6, out
     os.environ["LMC_RESORT_EVERY"] = "4" if relocate else "0"  # the periodic full re-sort by (technique, screen Morton code) rides along: every 4th step here
     try:
         p = gc.pkg()
-        ren = p.Renderer(gc.TORUS, force_diffuse=1, max_depth=max_depth, width=128, height=96, seed_offset=0, use_gradient=1 if gc.pathref() else 0)
+        ren = p.Renderer(gc.TORUS, force_diffuse=1, max_depth=max_depth, width=128, height=96, seed_offset=0, use_gradient=1)
         for k, v in opts.items():
             ren.set_option(k, v)
         if not mala:
@@ -126,7 +126,7 @@ def test_benchmarked_size_through_the_cache_ready_transition():
         os.environ["LMC_RELOCATE"] = "1" if relocate else "0"
         os.environ["LMC_RESORT_EVERY"] = "8" if relocate else "0"
         try:
-            ren = p.Renderer(gc.TORUS, force_diffuse=1, max_depth=6, seed_offset=0, use_gradient=1 if gc.pathref() else 0)
+            ren = p.Renderer(gc.TORUS, force_diffuse=1, max_depth=6, seed_offset=0, use_gradient=1)
             norm, nc = ren.init_chains(8 * n, n, 65536, 256)
         finally:
             del os.environ["LMC_RELOCATE"], os.environ["LMC_RESORT_EVERY"]
@@ -139,8 +139,7 @@ def test_benchmarked_size_through_the_cache_ready_transition():
         runs.append((st, rs, summ, film, norm))
     (st0, rs0, s0, f0, n0), (st1, rs1, s1, f1, n1) = runs
     assert n0 == n1 and rs0 is None and rs1 is not None and rs1["relocations"] >= 29 and rs1["skipped"] == 0
-    if gc.pathref():
-        assert st0["cacheReadyMask"] != 0 and st0["gradCalls"] > 0, "test set-up: the run never left the cache-fill phase"
+    assert st0["cacheReadyMask"] != 0 and st0["gradCalls"] > 0, "test set-up: the run never left the cache-fill phase"
     for k in ("steps", "largeSteps", "accepted", "resets", "cacheQueries", "cacheHits", "gradCalls", "cacheReadyMask"):
         assert st0[k] == st1[k], (k, st0[k], st1[k])
     sample = np.r_[np.arange(64), np.random.default_rng(0).choice(n, 4096, replace=False), np.arange(n - 64, n)]
