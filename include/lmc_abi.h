@@ -155,6 +155,17 @@ int lmc_relocation_stats(lmc_ctx *ctx, long long *out4);
 /* relocations skipped so far because their movers exceeded the staging records (N / 2 after the first full sort): such a step's movers stay where
  * they are -- a performance event only, visible here and as "chains moved by the last one" = 0; -1 when relocation is off */
 long long lmc_relocation_skipped(lmc_ctx *ctx);
+/* the resident schedule (lmc_set_option "resident_steps" = K >= 1; 0, the default, is lock step only; refused on H2MC contexts): once every
+ * relevant gradient cache is frozen -- from the step in which the last one becomes ready, mid-call included; plain MLT from the first step --
+ * lmc_chains_step / lmc_group_chains_step(n) run their remaining steps as ceil(remaining / K) launches (device/step_resident.hip) in which every
+ * chain advances by up to K complete mutations on its own (no other launch, no host round trip in between), and hand back to lock step with
+ * the next step's work lists built.  Same trajectories as lock step, chain for chain; the film differs only in the order of its float atomics.
+ * K is capped so that one launch stays in the tens of milliseconds.  "resident_lanes" (16 / 32 / 64; 0, the default: 32 up to 2^16 chains, 64
+ * above): chains per 64-lane wave.
+ * lmc_get_option "resident_guard": steps of resident launches that would have needed the gradient program or a cache push (0 by construction).
+ * out4 = [resident launches, chain-steps advanced by them, lock steps run, K in force] since lmc_chains_init; *kernel_ms (may be NULL): HIP-event
+ * time of the resident launches */
+int lmc_resident_stats(lmc_ctx *ctx, long long *out4, double *kernel_ms);
 /* kernel time (ms, HIP events on the launch stream) and launch count of the chain-step kernel since the last call */
 int lmc_step_timing(lmc_ctx *ctx, double *kernel_ms, long long *launches);
 /* split of the interval the last lmc_step_timing call covered: out3[0] = ms inside the lean small-step kernel

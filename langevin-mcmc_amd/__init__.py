@@ -58,6 +58,8 @@ def lib():
         L.lmc_chain_summary.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
         L.lmc_step_timing.argtypes = [vp, vp, vp]
         L.lmc_relocation_stats.argtypes = [vp, vp]
+        if hasattr(L, "lmc_resident_stats"):  # (an A/B library built from an older tree, LMC_LIB, has no resident schedule)
+            L.lmc_resident_stats.argtypes = [vp, vp, vp]
         if hasattr(L, "lmc_relocation_skipped"):  # (an older A/B build selected with LMC_LIB lacks it)
             L.lmc_relocation_skipped.argtypes = [vp]
             L.lmc_relocation_skipped.restype = c_ll
@@ -238,6 +240,15 @@ class Renderer:
             raise RuntimeError(_err())
         return dict(relocations=o[0], moved=o[1], breaks=o[2], slots=o[3], skipped=int(lib().lmc_relocation_skipped(self.h)) if hasattr(lib(), "lmc_relocation_skipped") else 0)
 
+    def resident_stats(self):
+        """The resident schedule (set_option("resident_steps", K)) since init_chains: resident launches, chain-steps they advanced, lock steps run,
+        K in force (after the cap), HIP-event ms of the resident launches, and the guard: steps that would have needed a gradient / cache push (0)"""
+        o = (c_ll * 4)()
+        ms = ctypes.c_double()
+        if lib().lmc_resident_stats(self.h, o, ctypes.byref(ms)) != 0:
+            raise RuntimeError(_err())
+        return dict(launches=o[0], chain_steps=o[1], lock_steps=o[2], k=o[3], kernel_ms=ms.value, guard=int(self.get_option("resident_guard")))
+
     def summary(self, which=0):
         n = self.num_chains  # which = 0: current states, 1: init states -- of this rank's chains
         out = np.zeros((n, 32), np.float32)
@@ -314,6 +325,13 @@ class Group:
         L.lmc_group_chains_step.argtypes = [vp, ctypes.c_int, ctypes.c_int]
         if L.lmc_group_chains_step(self._arr, len(self.rens), n) != 0:
             raise RuntimeError("lmc_group_chains_step failed: " + _err())
+
+    def resident_stats(self):
+        """resident_stats() of the members combined: launches, chain-steps, kernel ms and guard summed; lock steps and K of member 0 (equal on all)"""
+        st = [r.resident_stats() for r in self.rens]
+        out = {k: sum(d[k] for d in st) for k in ("launches", "chain_steps", "kernel_ms", "guard")}
+        out.update(lock_steps=st[0]["lock_steps"], k=st[0]["k"], members=st)
+        return out
 
     def info(self):
         """distinct devices, ordered device pairs, pairs with direct peer access enabled, host threads driving the steps"""

@@ -64,6 +64,10 @@ void LaunchStepSmallLeanGrad(const lmcd::DScene &S, const lmcd::DCache *cache, c
 void LaunchStepSmallPlain(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P,
                           const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads,
                           bool profile, hipStream_t s);
+// the resident schedule (step_resident.h / .hip): every chain of the slot arrays advances by up to maxSteps complete mutations in ONE launch (caches frozen);
+// lanes = active chains per 64-lane wave (16 / 32 / 64); guard[0] += chain-steps run, guard[1] += steps that would have needed the gradient program or a cache push
+void LaunchStepResident(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P, int maxSteps,
+                        int lanes, unsigned long long *guard, bool glossy, int mux, int bvhStackNeed, hipStream_t s);
 // all small steps of an H2MC render: the launches of the wave-cooperative pipeline (device/dh2coop.h; step_h2_phases.hip, h2hess.hip, h2gauss.hip)
 void LaunchH2Begin(const lmcd::DScene &S, const lmcd::ChainArrays &A, const lmcd::StepParams &P, const lmcd::H2Arrays &H, const int *list, const int *listCount, int gridBlocks,
                    hipStream_t s);

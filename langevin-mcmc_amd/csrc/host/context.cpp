@@ -246,6 +246,15 @@ struct lmc_ctx {
     char *treePinned[CACHE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t treesUpEvent = nullptr;
     bool allCachesReady = false;
+    // the resident schedule (device/step_resident.h, RunResident): 0 = lock step only; K >= 1 = once the caches are frozen, up to K mutations
+    // of every chain per launch.  residentLanes: active chains per 64-lane wave ("resident_lanes"; 0 = ResidentLanes' choice); the rest is bookkeeping for
+    // lmc_resident_stats
+    int residentSteps = 0, residentLanes = 0;
+    long long residentLaunches = 0, lockSteps = 0;
+    double residentMs = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> residentEvents;  // one pair per resident launch not yet read by lmc_resident_stats
+    DevBuf<unsigned long long> residentGuard;                       // [chain-steps of resident launches, steps that would have needed a gradient / push]
+    bool residentResortPending = false;                             // a full re-sort is due before the next lock step (relocation on)
     int mutationAtInit = -1;  // (mala, h2mc) the resident chain state was laid out for by lmc_chains_init; lmc_chains_step refuses any other
     bool needGeneric = true;  // some chain may still need the generic small-step launch (gradient / deep cache tree)
     bool genericTokenOnly = false;  // ... but only as the fallback of the lean launch without light sub-paths: a few blocks, no list sort
@@ -298,6 +307,7 @@ struct lmc_ctx {
             if (e) (void)hipEventDestroy(e);
         for (auto st : sideStream)
             if (st) (void)hipStreamDestroy(st);
+        for (auto &e : residentEvents) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -631,7 +641,14 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
     else if (n == "exp_resort") c->pendingResort = (int)v;
     else if (n == "resort_every") c->resortEveryOpt = std::max(0, (int)v);  // period of the full re-sort (relocate.hip); takes effect at the next lmc_chains_init; overrides LMC_RESORT_EVERY
     else if (n == "resort_first") c->resortFirstOpt = std::max(0, (int)v);
-    else throw std::runtime_error("Unknown dpt option:" + n);
+    else if (n == "resident_steps") {  // the resident schedule (RunResident); takes effect at the next lmc_chains_step
+        if (o.h2mc && v > 0) throw std::runtime_error("resident_steps: H2MC contexts run in lock step only (their small step is the wave-cooperative pipeline)");
+        if (v < 0 || v > 1e6) throw std::runtime_error("resident_steps: K >= 0 expected (0 = lock step)");
+        c->residentSteps = (int)v;
+    } else if (n == "resident_lanes") {
+        if (v != 0 && v != 16 && v != 32 && v != 64) throw std::runtime_error("resident_lanes: 16, 32 or 64 chains per 64-lane wave (0: by the number of chains)");
+        c->residentLanes = (int)v;
+    } else throw std::runtime_error("Unknown dpt option:" + n);
     SyncOptions(c);
     return 0;
     LMC_CATCH(-1)
@@ -658,7 +675,13 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "samplecache") *v = o.sampleFromGlobalCache ? 1 : 0;
     else if (n == "bvh_quantised") *v = c->S.qnodes ? 1 : 0;            // back-end state, not a <dpt> option: the node format of the scene's hot launches ...
     else if (n == "bvh_thick_flat_share") *v = c->thickFlatShare;       // ... and the figure it was chosen by (UploadScene)
-    else throw std::runtime_error("Unknown dpt option:" + n);
+    else if (n == "resident_steps") *v = c->residentSteps;
+    else if (n == "resident_lanes") *v = c->residentLanes;
+    else if (n == "resident_guard") {  // steps of resident launches that would have needed the gradient program or pushed to the cache (must stay 0)
+        HIP_CHECK(hipSetDevice(c->device));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        *v = c->residentGuard.p ? (double)c->residentGuard.Download()[1] : 0.0;
+    } else throw std::runtime_error("Unknown dpt option:" + n);
     return 0;
     LMC_CATCH(-1)
 }
@@ -1183,6 +1206,10 @@ void InitPhase4(lmc_ctx *c, InitJob &J) {
     memset(&c->cacheHost, 0, sizeof(c->cacheHost));
     UploadCacheStruct(c);
     c->allCachesReady = false;
+    c->residentGuard.Alloc(4);  // zero-filled
+    c->residentLaunches = 0, c->lockSteps = 0, c->residentMs = 0, c->residentResortPending = false;
+    for (auto &e : c->residentEvents) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+    c->residentEvents.clear();
     c->stepsSinceCounts = 0;
     for (int sl = 0; sl < CACHE_SLOTS; sl++) c->lastCounts[sl] = 0, c->lastDelta[sl] = 0, c->rowsPrefetched[sl] = false;
     c->needGeneric = true;
@@ -1247,6 +1274,7 @@ void InitPhase4(lmc_ctx *c, InitJob &J) {
     c->parity = 0;
     // every chain begins with a forced large step (mlt.h:121: the resampled init states only feed the outlier reset)
     LaunchInitLists((int)N, c->lists[0][0].p, c->listCounts[0].p, s);
+    HIP_CHECK(hipMemsetAsync(c->nextKind.p, NEXT_LARGE, N, s));  // ... and so does A.nextKind say, which the resident launch reads (RunResident)
     HIP_CHECK(hipMemsetAsync(c->film.p, 0, c->film.n * sizeof(float), s));
     HIP_CHECK(hipStreamSynchronize(s));
     WarmStepLaunches(c);
@@ -1875,11 +1903,11 @@ void DebugResort(lmc_ctx *c) {
 // second half: the gathered pushes applied (a cache that becomes ready at the end of this step -- mlt.cpp: push() flips is_ready
 // inside the step -- is seen by the list build: chains whose next step no longer needs a gradient go to the lean launch right
 // away), then the work lists of the next step
+void BuildNextLists(lmc_ctx *c, int nxt);
 void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int nxt = 1 - c->parity;
-    NextLists next{c->lists[nxt][0].p, c->lists[nxt][1].p, c->lists[nxt][2].p, c->listCounts[nxt].p};
     if (exchanged) {
         if (!c->appliedEarly) CacheApplyLaunch(c, s);
         CacheApplyFinish(c);
@@ -1901,6 +1929,17 @@ void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
         }
     }
     c->stepsSinceInit++;
+    BuildNextLists(c, nxt);
+    c->parity = nxt;
+    if (c->timing) {
+        HIP_CHECK(hipEventRecord(ev.e[3], s));
+        c->events.push_back(ev);
+    }
+}
+// the work lists of the step that runs next, into lists[nxt] (their counts zeroed by the caller), on the step stream
+void BuildNextLists(lmc_ctx *c, int nxt) {
+    hipStream_t s = c->stream;
+    NextLists next{c->lists[nxt][0].p, c->lists[nxt][1].p, c->lists[nxt][2].p, c->listCounts[nxt].p};
     const int sortPlain = c->relocate ? 0 : c->sortPlain;  // relocated chains are grouped already, and in place
     LaunchBuildLists(c->A, next, sortPlain == 4 ? 0 : sortPlain, LeanDims(c) | (c->S.opt.leanLightless ? 1u << 31 : 0u), s);
     if (sortPlain == 4) {  // A/B: the lean list grouped by technique over the WHOLE list (a wave then retraces one technique; its lanes' state lines are anywhere)
@@ -1916,11 +1955,6 @@ void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
     if (c->needGeneric && c->S.opt.h2mc && c->overlap && c->h2Parts >= 2) {  // the two halves of the H2MC pipeline's list (LaunchGeneric), while nothing else runs
         LaunchSplitList(c->lists[nxt][1].p, c->listCounts[nxt].p + 1, c->h2Parts, c->h2SubList.p, c->h2PartStride, c->h2SubCount.p, c->stepGrid * 4 + 1, s);
         c->h2SplitOf = c->lists[nxt][1].p;
-    }
-    c->parity = nxt;
-    if (c->timing) {
-        HIP_CHECK(hipEventRecord(ev.e[3], s));
-        c->events.push_back(ev);
     }
 }
 }  // namespace
@@ -1951,6 +1985,74 @@ static void WarmStepLaunches(lmc_ctx *c) {
 }
 extern "C++" {
 namespace {
+// ---- the resident schedule (lmc_set_option "resident_steps" = K; device/step_resident.h)
+// Cap of K: one resident launch runs at most kResidentBudget chain-steps and at most kResidentMaxK steps per chain, so that it stays in the tens of
+// milliseconds -- it holds its waves for the whole launch, and a render is cut into launches the host can stop between.  Measured
+// (profiles/r07_resident_sweep*.jsonl): a resident step of the slowest workload (veach-door LMC) takes 1.1 ms at 2^14 chains and 1.3 ms at 2^16, a
+// launch of 2^21 chain-steps 25 .. 45 ms at 2^16 .. 2^20; K = 128 gained at most 5 % over 32 while its launches took 100 .. 240 ms.
+// The number of active lanes per wave (ResidentLanes): 32 up to 2^16 chains, where a wave slot is free and fewer lanes mean less large / small and
+// path-length divergence per wave (veach-door LMC +12 %, plain MLT +14 % at 2^16 against 64); 64 above (at 2^18 32 lanes cost 35 .. 45 %).
+constexpr long long kResidentBudget = 1ll << 21;
+constexpr int kResidentMaxK = 32;
+int ResidentLanes(const lmc_ctx *c) { return c->residentLanes ? c->residentLanes : c->N <= 65536 ? 32 : 64; }
+int ResidentK(const lmc_ctx *c) {
+    if (c->residentSteps <= 0 || c->N <= 0) return 0;
+    const long long byBudget = std::max(1ll, kResidentBudget / (long long)c->N);
+    return (int)std::min<long long>({(long long)c->residentSteps, (long long)kResidentMaxK, byBudget});
+}
+// May this member's remaining steps run resident?  Not while a relevant cache dim is filling: the lock-step contract orders the pushes by step
+// (mlt.cpp:120-127).  CachePending is what StepPhase1 would ask at the head of this very step (it sets allCachesReady from the step in which the
+// last cache became ready); plain MLT never fills a cache, so its chains run resident from the first step.
+bool ResidentEligible(lmc_ctx *c) {
+    if (c->residentSteps <= 0 || c->S.opt.h2mc) return false;
+    return c->allCachesReady || !CachePending(c);
+}
+// `steps` mutations of every chain as ceil(steps / K) resident launches on the step stream, then the hand-back to lock step: the next step's work
+// lists from A.nextKind (every resident step ended with QueueNext) and stepsSinceInit advanced by the steps run.
+void RunResident(lmc_ctx *c, int steps) {
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    c->filmReduced = false;
+    const int K = ResidentK(c);
+    Film film{c->film.p, c->S.cam.width, c->S.cam.height};
+    const StepParams P = MakeStepParams(c);
+    const int mux = c->S.opt.sampleCache ? 2 : c->scene->options.largeStepMultiplexed ? 1 : 0;
+    static const bool resortBetween = getenv("LMC_RESIDENT_RESORT") && atoi(getenv("LMC_RESIDENT_RESORT")) != 0;  // A/B: the full re-sort between resident launches
+    std::pair<hipEvent_t, hipEvent_t> ev;
+    HIP_CHECK(hipEventCreate(&ev.first));
+    HIP_CHECK(hipEventCreate(&ev.second));
+    c->residentEvents.push_back(ev);
+    HIP_CHECK(hipEventRecord(ev.first, s));
+    for (int done = 0; done < steps;) {
+        const int k = std::min(K, steps - done);
+        LaunchStepResident(c->S, c->cacheDev.p, c->A, film, P, k, ResidentLanes(c), c->residentGuard.p, c->S.glossy != 0, mux, c->largeLdsStack ? c->bvhDepth : 1 << 30, s);
+        HIP_CHECK(hipGetLastError());
+        c->residentLaunches++;
+        c->stepsSinceInit += k;
+        done += k;
+        if (resortBetween && done < steps && c->relocate && c->resortEvery > 0 && c->RB.capacity >= (int)c->N) LaunchRelocFullSort(c->A, c->S.opt.maxDepth, c->RB, c->RS, s), c->resorts++;
+    }
+    HIP_CHECK(hipEventRecord(ev.second, s));
+    const int nxt = 1 - c->parity;
+    HIP_CHECK(hipMemsetAsync(c->listCounts[nxt].p, 0, 4 * sizeof(int), s));
+    BuildNextLists(c, nxt);
+    c->parity = nxt;
+    // The resident launches skipped the per-step relocation: the chains' slots no longer follow their techniques.  Slot order is a performance matter
+    // only (every result is per chain; lmc_chain_summary reports rows in chain order), so the re-sort waits for the next lock step (ResumeLockStep).
+    c->residentResortPending = c->relocate;
+}
+// ahead of a lock step after resident launches: the full re-sort (relocate.hip) the resident run left due, and the lists rebuilt for the new slots
+void ResumeLockStep(lmc_ctx *c) {
+    if (!c->residentResortPending) return;
+    c->residentResortPending = false;
+    if (!c->relocate || c->resortEvery <= 0 || c->RB.capacity < (int)c->N) return;
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    LaunchRelocFullSort(c->A, c->S.opt.maxDepth, c->RB, c->RS, s);
+    c->resorts++;
+    HIP_CHECK(hipMemsetAsync(c->listCounts[c->parity].p, 0, 4 * sizeof(int), s));
+    BuildNextLists(c, c->parity);
+}
 void RunSteps(const std::vector<lmc_ctx *> &g, int nSteps) {
     for (lmc_ctx *c : g) CheckSteppable(c);
     typedef std::chrono::steady_clock Clock;
@@ -1958,6 +2060,13 @@ void RunSteps(const std::vector<lmc_ctx *> &g, int nSteps) {
     if (g.size() == 1 || !GroupThreads()) {  // one rank (of an RCCL job or on its own), or the A/B form of a group: every member from this thread
         std::vector<lmc_ctx::StepEvents> ev(g.size());
         for (int it = 0; it < nSteps; it++) {
+            bool resident = true;  // equal on all members: they hold the same cache at every step
+            for (lmc_ctx *c : g) resident = ResidentEligible(c) && resident;
+            if (resident) {
+                for (lmc_ctx *c : g) RunResident(c, nSteps - it);
+                break;
+            }
+            for (lmc_ctx *c : g) ResumeLockStep(c), c->lockSteps++;
             const auto t0 = Clock::now();
             bool exchange = false;
             for (size_t k = 0; k < g.size(); k++) {
@@ -1979,6 +2088,12 @@ void RunSteps(const std::vector<lmc_ctx *> &g, int nSteps) {
             lmc_ctx *c = g[k];
             lmc_ctx::StepEvents ev;
             for (int it = 0; it < nSteps; it++) {
+                if (ResidentEligible(c)) {  // the same step on every member (same cache); from here on no member meets another
+                    RunResident(c, nSteps - it);
+                    break;
+                }
+                ResumeLockStep(c);
+                c->lockSteps++;
                 const auto t0 = Clock::now();
                 const bool fill = !c->allCachesReady;  // equal on all members: they hold the same cache at every step
                 const bool e = StepPhase1(c, ev);
@@ -2356,6 +2471,23 @@ int lmc_relocation_stats(lmc_ctx *c, long long *out4) {
     out4[0] = c->relocations, out4[1] = c->relocations ? c->relocCount.Download()[0] : 0, out4[2] = breaks, out4[3] = (long long)N;
     return 0;
     LMC_CATCH(-2)
+}
+
+int lmc_resident_stats(lmc_ctx *c, long long *out4, double *kernelMs) {
+    LMC_TRY
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (auto &e : c->residentEvents) {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e.first, e.second));
+        c->residentMs += ms;
+        (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+    }
+    c->residentEvents.clear();
+    out4[0] = c->residentLaunches, out4[1] = c->residentGuard.p ? (long long)c->residentGuard.Download()[0] : 0, out4[2] = c->lockSteps, out4[3] = ResidentK(c);
+    if (kernelMs) *kernelMs = c->residentMs;
+    return 0;
+    LMC_CATCH(-1)
 }
 
 long long lmc_relocation_skipped(lmc_ctx *c) {

@@ -3,7 +3,9 @@
 // output naming (<film filename>_timeuse_<seconds>s.exr written next to the scene, mlt.cpp:208) and the same stdout
 // lines ("Average brightness:", "Elapsed time:", "Done!").  Only integrator = mcmc with mala = true (the LMC path) is
 // served; anything else is refused.  Extra flags (not in the reference): --chains N (Markov chains resident on the GPUs,
-// default: <dpt numchains>), --init-threads V (MLTInit streams, default 65536), --device D, --force-diffuse, --maxdepth D, and
+// default: <dpt numchains>), --init-threads V (MLTInit streams, default 65536), --device D, --force-diffuse, --maxdepth D, --resident K (the
+// resident schedule, lmc_set_option "resident_steps": up to K mutations of every chain per launch once the gradient caches are frozen; H2MC
+// renders stay in lock step), and
 // --gpus N (devices 0 .. N-1) / --devices a,b,.. (an explicit list; a device may appear more than once: bring-up on one GPU): the chains are
 // sharded over the listed devices as ranks of ONE job (lmc_group_*: MLTInit sharded by init stream, contiguous chain-id ranges, the gradient
 // cache's pushes exchanged while it fills -- the trajectories of a single device holding all the chains), and the per-device films are summed
@@ -29,7 +31,7 @@ static double Opt(lmc_ctx *ctx, const char *name) {
 int main(int argc, char *argv[]) {
     if (argc <= 1) return 0;
     printf("Langevin MCMC dpt (MI355X back end)\n");
-    int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8;
+    int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8, resident = 0;
     long long chains = 0;
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -56,6 +58,7 @@ int main(int argc, char *argv[]) {
             }
         } else if (a == "--force-diffuse") forceDiffuse = 1;
         else if (a == "--maxdepth") maxDepth = std::stoi(argv[++i]);
+        else if (a == "--resident") resident = std::stoi(argv[++i]);
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -86,6 +89,13 @@ int main(int argc, char *argv[]) {
             fprintf(stderr, "dpt_amd serves the LMC path only (<dpt> integrator=mcmc with mala=true or h2mc=true)\n");
             return 1;
         }
+        if (resident > 0 && Opt(ctx, "h2mc") != 0) printf("--resident: H2MC renders run in lock step\n");
+        else if (resident > 0)
+            for (lmc_ctx *c : ctxs)
+                if (lmc_set_option(c, "resident_steps", resident) != 0) {
+                    fprintf(stderr, "%s\n", lmc_last_error());
+                    return 1;
+                }
         int info[8];
         lmc_info(ctx, info);
         const int W = info[0], H = info[1];
