@@ -64,11 +64,13 @@ int lmc_scene_params(lmc_ctx *ctx, float *out38);
  * at any time, but once one of them differs from its value at lmc_chains_init, lmc_chains_step returns -1 until the chains are initialised again.
  * Back-end switches (no counterpart in the reference): "timing" (per-step HIP events for lmc_step_timing), "overlap" (side streams on / off),
  * "max-derivatives-depth" (main.cpp:59-60), "resort_every" / "resort_first" (period and first step of the full re-sort of the resident chains by
- * technique and screen position, device/relocate.hip; default 32 / 4, 0 = off; read at the next lmc_chains_init), "exp_resort" (measurement hook) */
+ * technique and screen position, device/relocate.hip; default 32 / 4, 0 = off; read at the next lmc_chains_init), "exp_resort" (measurement hook),
+ * "bidirectional" (the generator of lmc_mc_render) */
 int lmc_set_option(lmc_ctx *ctx, const char *name, double value);
 /* <dpt> options as parsed: spp, numinitsamples, numchains, directspp, mindepth, maxdepth, largestepprob, largestepscale,
  * mala, h2mc, seedoffset (dptoptions.h:7-34); back-end state: bvh_quantised (the scene's hot launches walk the 64-byte quantised BVH nodes),
- * bvh_thick_flat_share (the figure that choice is made by) */
+ * bvh_thick_flat_share (the figure that choice is made by); integrator_mc (1 when <string integrator> is "mc"), bidirectional (the <dpt> value,
+ * which lmc_set_option "bidirectional" overrides) */
 int lmc_get_option(lmc_ctx *ctx, const char *name, double *value);
 /* film "filename" of the scene (outputName); the reference appends "_timeuse_<seconds>s.exr" (mlt.cpp:208) */
 const char *lmc_output_name(lmc_ctx *ctx);
@@ -135,6 +137,17 @@ int lmc_path_trace(lmc_ctx *ctx, int spp);
 /* plain Monte Carlo over GeneratePathBidir samples (path length >= 3), radiance image through lmc_direct_read: a second
  * cross-check estimator that isolates the bidirectional generator from the Markov chain */
 int lmc_bidir_mc(lmc_ctx *ctx, int spp);
+/* The "mc" integrator (PathTrace, pathtrace.cpp:14-78): spp samples per pixel, GeneratePathBidir with a fixed pixel when <dpt bidirectional>
+ * is true, GeneratePath otherwise, over the scene's [mindepth, maxdepth]; every contribution with luminance above 1e-10 splatted with weight
+ * 1 / spp into a film of its own (neither the MLT film nor the direct film; no chain state is touched).  Stream (t, s) = RNG(t + nTiles * s +
+ * seedoffset), t the 16x16 tile index, s the sample index, draws sample s of every pixel of tile t; lmc_mc_render clears the MC film and
+ * renders the stream ids [stream_begin, stream_end) of [0, nTiles * spp) (stream_end = -1: all), so films of disjoint ranges sum to the
+ * film of their union.  With spp = 1 and seedoffset 0 the streams are the reference's own. */
+int lmc_mc_render(lmc_ctx *ctx, int spp, long long stream_begin, long long stream_end);
+/* the MC film, W*H*3 floats, already weighted by 1 / spp */
+int lmc_mc_read(lmc_ctx *ctx, float *rgb);
+/* out2[0] = paths traced, out2[1] = contributions splatted, by the last lmc_mc_render */
+int lmc_mc_stats(lmc_ctx *ctx, long long *out2);
 /* out[0..7] = steps, largeSteps, accepted, gradCalls, cacheQueries, cacheHits, resets, cacheReadyMask; *weight_sum =
  * sum over steps of the splatted weight (film luminance == normalization * weight_sum) */
 int lmc_stats(lmc_ctx *ctx, long long *out8, double *weight_sum);

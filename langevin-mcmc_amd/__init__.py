@@ -74,6 +74,10 @@ def lib():
         L.lmc_direct_read.argtypes = [vp, vp]
         L.lmc_path_trace.argtypes = [vp, ctypes.c_int]
         L.lmc_bidir_mc.argtypes = [vp, ctypes.c_int]
+        if hasattr(L, "lmc_mc_render"):  # (an A/B library built from an older tree, LMC_LIB, has no mc integrator)
+            L.lmc_mc_render.argtypes = [vp, ctypes.c_int, c_ll, c_ll]
+            L.lmc_mc_read.argtypes = [vp, vp]
+            L.lmc_mc_stats.argtypes = [vp, vp]
         L.lmc_stream_probe.argtypes = [c_ll, ctypes.c_int]
         L.lmc_grad_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
         L.lmc_trace.argtypes = [vp, ctypes.c_int, vp, vp, vp]
@@ -219,6 +223,25 @@ class Renderer:
         if lib().lmc_direct_read(self.h, P(out)) != 0:
             raise RuntimeError(_err())
         return out
+
+    def mc_render(self, spp, streams=None):
+        """The scene's "mc" integrator (PathTrace): spp samples per pixel, bidirectional or not as the scene says (set_option "bidirectional"
+        overrides it); radiance image [H, W, 3], already weighted by 1 / spp.  streams=(begin, end): only those stream ids of
+        [0, nTiles * spp) (end -1: to the last one); the films of disjoint ranges sum to the film of their union."""
+        begin, end = (0, -1) if streams is None else (int(streams[0]), int(streams[1]))
+        if lib().lmc_mc_render(self.h, int(spp), begin, end) != 0:
+            raise RuntimeError(_err())
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        if lib().lmc_mc_read(self.h, P(out)) != 0:
+            raise RuntimeError(_err())
+        return out
+
+    def mc_stats(self):
+        """(paths traced, contributions splatted) of the last mc_render"""
+        o = (c_ll * 2)()
+        if lib().lmc_mc_stats(self.h, o) != 0:
+            raise RuntimeError(_err())
+        return int(o[0]), int(o[1])
 
     def stats(self):
         s = (c_ll * 8)()

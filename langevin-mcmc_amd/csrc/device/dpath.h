@@ -397,9 +397,21 @@ LMC_D int HitLightOf(const DScene &S, bool hitSurface, const SurfHit &hit) {  //
 #endif
 }
 
-// GeneratePathBidir, path.cpp:1237-1449 with screenPosi = (-1,-1)
-template <class Stk>
-LMC_D void GeneratePathBidir(const DScene &S, int minDepth, int maxDepth, DPath &path, ContribSink &sink, Rng &rng, Stk &stk) {
+// EmitFromCameraInit's screen position (path.cpp:542-552) from the two draws `u` (RndVec2 order): screenPosi = (-1,-1), the whole
+// screen (MLT, lmc_bidir_mc) ...
+struct RandomScreen {
+    LMC_D V2 operator()(const DScene &, V2 u) const { return u; }
+};
+// ... or a fixed pixel (x + u) / W, (y + u') / H (the mc integrator, pathtrace.cpp:48-55)
+struct PixelScreen {
+    int x, y;
+    LMC_D V2 operator()(const DScene &S, V2 u) const { return V2{(x + u.x) / float(S.cam.width), (y + u.y) / float(S.cam.height)}; }
+};
+
+// GeneratePathBidir, path.cpp:1237-1449.  Sink: anything with Push(const Contrib &) (ContribSink: the MLT callers; McSink, mc.hip);
+// Screen: RandomScreen (screenPosi = (-1,-1)) or PixelScreen.
+template <class Stk, class Sink = ContribSink, class Screen = RandomScreen>
+LMC_D void GeneratePathBidir(const DScene &S, int minDepth, int maxDepth, DPath &path, Sink &sink, Rng &rng, Stk &stk, Screen screen = Screen()) {
     TraceOcclusion trace;
     path.camCount = path.lgtCount = 0;
     path.envPrim = -1;
@@ -452,8 +464,8 @@ LMC_D void GeneratePathBidir(const DScene &S, int minDepth, int maxDepth, DPath 
     }
 
     BPS cps;
-    {  // EmitFromCameraInit with screenPosi = (-1,-1): Vector2(u, u), right-to-left
-        V2 s = RndVec2(rng);
+    {  // EmitFromCameraInit: Vector2(f(u), g(u)), right-to-left
+        V2 s = screen(S, RndVec2(rng));
         path.screen0 = s.x, path.screen1 = s.y;
     }
     V2 screenPos{path.screen0, path.screen1};

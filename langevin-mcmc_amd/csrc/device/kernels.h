@@ -46,6 +46,10 @@ void LaunchInitRegen(const lmcd::DScene &S, int numChains, long long perThread, 
 void LaunchDirect(const lmcd::DScene &S, const lmcd::Film &film, int directSpp, int minDepth, int maxDepth, int bvhDepth, bool waveKernel, uint32_t *tabScratch,
                   hipStream_t s);
 void LaunchBidirMC(const lmcd::DScene &S, const lmcd::Film &film, int nThreads, int samplesPerThread, uint32_t *tabScratch, float *contribScratch, hipStream_t s);
+// the mc integrator (mc.hip): stream ids [streamBegin, streamEnd) of nTiles * spp; tabScratch: 64 words per thread (MCThreads), counters: 2 x u64
+void LaunchMC(const lmcd::DScene &S, const lmcd::Film &film, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin, long long streamEnd,
+              uint32_t *tabScratch, unsigned long long *counters, hipStream_t s);
+long long MCThreads(const lmcd::DScene &S, long long streamBegin, long long streamEnd);
 void LaunchSetupChains(const lmcd::ChainArrays &A, int chainBegin, long long perChain, long long chainsNeedExtra, hipStream_t s);
 void LaunchFirstKind(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::StepParams &P, hipStream_t s);
 // one of the three step launches (device/step_*.hip): chains of `list` (count read on the device) run one mutation and

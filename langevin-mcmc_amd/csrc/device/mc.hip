@@ -1,0 +1,161 @@
+// The "mc" integrator: the reference's PathTrace (pathtrace.cpp:14-78) -- spp samples of every pixel, GeneratePathBidir with a fixed
+// pixel when <dpt bidirectional> is true (the default), GeneratePath (DirectSample, ddirect.h) otherwise; every contribution with
+// luminance above 1e-10 is splatted with weight 1 / spp.
+//
+// Streams.  Stream (t, s) = RNG(t + nTiles * s + seedOffset), t the 16x16 tile index (ty * nXTiles + tx, pathtrace.cpp:39-40), s in [0, spp)
+// the sample index; it draws sample s of every pixel of tile t in the reference's pixel order (rows y0..y1, then x0..x1).  With spp = 1 and
+// seedOffset 0 that is the reference's own loop (one RNG(tileIndex) per tile).  A launch renders a contiguous range [begin, end) of stream
+// ids t + nTiles * s, so the image does not depend on the launch geometry or on how the range is split over devices.
+//
+// Lanes.  Thread g walks stream (t, s) = (g / nS, sBase + g % nS): the samples of one tile sit side by side in a wave and walk the same
+// pixel at the same time.  A sample's camera-side contributions all land in its own pixel; they are summed in the lane and the lanes of a
+// wave that share a pixel add once (wave reduction) instead of 64 times to the same three floats (MI355X_MICROARCH.md: many adders on one
+// row run ~14x slower).  Light-tracing contributions (ConnectToCamera) land anywhere and are added on the spot.
+#include "kernels.h"
+#include "ddirect.h"
+
+using namespace lmcd;
+
+namespace {
+
+constexpr float kMcMinLuminance = 1e-10f;  // pathtrace.cpp:60
+
+// where one sample's contributions go: the camera-side ones into the lane's own-pixel sum, the rest straight to the film
+struct McSink {
+    Film film;
+    float spp;  // contrib / spp: a division, as Eigen's vector / scalar in the reference
+    V3 acc;
+    int accPix;   // film index of the own-pixel sum, -1 while empty
+    unsigned splats;
+    LMC_D static int PixelOf(const Film &f, V2 sp) {  // Splat's nearest pixel (dchain.h)
+        const int ix = Clampi((int)(sp.x * f.W), 0, f.W - 1), iy = Clampi((int)(sp.y * f.H), 0, f.H - 1);
+        return iy * f.W + ix;
+    }
+    LMC_D void Add(bool ownPixel, V2 sp, V3 contrib) {
+        if (Luminance(contrib) <= kMcMinLuminance) return;
+        if (!AllFinite(contrib)) return;  // Splat drops it (image.h:66-77)
+        const V3 c{contrib.x / spp, contrib.y / spp, contrib.z / spp};
+        splats++;
+        const int pix = PixelOf(film, sp);
+        if (ownPixel && (accPix < 0 || accPix == pix)) {
+            accPix = pix;
+            acc = acc + c;
+            return;
+        }
+        float *px = film.rgb + (size_t)pix * 3;
+        unsafeAtomicAdd(px + 0, c.x), unsafeAtomicAdd(px + 1, c.y), unsafeAtomicAdd(px + 2, c.z);
+    }
+    LMC_D void Push(const Contrib &c) { Add(c.camDepth != 1, c.screenPos, c.contrib); }  // camDepth 1: ConnectToCamera (light tracing)
+    LMC_D void operator()(V2 sp, V3 contrib) { Add(true, sp, contrib); }                 // GeneratePath: camera side only
+};
+
+LMC_D float WaveSum(float v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// every lane of the wave arrives here (converged): the own-pixel sums of the wave committed, one add per pixel for the lanes that share one
+LMC_D void CommitOwnPixel(const Film &film, McSink &sink, int lane) {
+    const int key = sink.accPix;
+    unsigned long long pending = __ballot(key >= 0);
+    for (int round = 0; pending && round < 4; round++) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int lk = __shfl(key, leader);
+        const bool mine = key == lk && key >= 0;
+        const unsigned long long group = __ballot(mine);
+        if (__popcll(group) < 2) break;  // lanes on different pixels: plain atomics below
+        const float rx = WaveSum(mine ? sink.acc.x : 0.f), ry = WaveSum(mine ? sink.acc.y : 0.f), rz = WaveSum(mine ? sink.acc.z : 0.f);
+        if (lane == leader) {
+            float *px = film.rgb + (size_t)lk * 3;
+            unsafeAtomicAdd(px + 0, rx), unsafeAtomicAdd(px + 1, ry), unsafeAtomicAdd(px + 2, rz);
+        }
+        if (mine) sink.accPix = -1;
+        pending &= ~group;
+    }
+    if (sink.accPix >= 0) {
+        float *px = film.rgb + (size_t)sink.accPix * 3;
+        unsafeAtomicAdd(px + 0, sink.acc.x), unsafeAtomicAdd(px + 1, sink.acc.y), unsafeAtomicAdd(px + 2, sink.acc.z);
+    }
+    sink.accPix = -1;
+    sink.acc = V3{0, 0, 0};
+}
+
+LMC_D unsigned long long WaveSumU64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// LMC_MC_MIN_WAVES: the waves per SIMD the register allocation must leave room for.  3 (at most 168 VGPRs): bidirectional renders at 64 spp
+// take 13 % (torus) / 22 % (veach-door) less time than with the free allocation (208 VGPRs, 2 waves) and than 4 (128 VGPRs, more scratch traffic); the
+// unidirectional kernel needs ~150 either way (profiles/r07_mc_ab_*.jsonl, scripts/build_variant.sh)
+#ifndef LMC_MC_MIN_WAVES
+#define LMC_MC_MIN_WAVES 3
+#endif
+
+// counters: [paths traced, contributions splatted]
+template <bool GLOSSY, bool BIDIR>
+__global__ void __launch_bounds__(64, LMC_MC_MIN_WAVES) k_mc(DScene S, Film film, int spp, int nXTiles, int nTiles, long long sBase, int nS, long long streamBegin,
+                                           long long streamEnd, int minDepth, int maxDepth, uint32_t *tabScratch, unsigned long long *counters) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const long long t = g / nS, s = sBase + g % nS;
+    const long long id = t + (long long)nTiles * s;
+    const bool active = t < nTiles && id >= streamBegin && id < streamEnd;
+    int x0 = 0, y0 = 0, tw = 0, th = 0;
+    Rng rng;
+    rng.tab = tabScratch + (size_t)g * 64;  // only written if the stream ticks (once per 2^32 draws)
+    rng.ticks = 0;
+    rng.state = 0;
+    if (active) {
+        const int tx = (int)(t % nXTiles), ty = (int)(t / nXTiles);
+        x0 = tx * 16, y0 = ty * 16;
+        tw = min(x0 + 16, S.cam.width) - x0, th = min(y0 + 16, S.cam.height) - y0;
+        const uint64_t seed = (uint64_t)(id + S.opt.seedOffset);
+        rng.SetSynth(seed);                    // the extension table synthesised from the seed (drng.h), not written to memory
+        rng.state = PcgAdvance(rng.s0, 64);    // RNG(seed)'s first state: 64 LCG steps (the table fill) behind S0
+    }
+    const int nPix = tw * th;
+    McSink sink{film, (float)spp, V3{0, 0, 0}, -1, 0u};
+    LocalStackT<GLOSSY> stk;
+    DPath path;
+    unsigned paths = 0;
+    for (int k = 0; __ballot(k < nPix); k++) {
+        if (k < nPix) {
+            const int x = x0 + k % tw, y = y0 + k / tw;  // rows y0..y1, then x0..x1
+            if (BIDIR) GeneratePathBidir(S, minDepth, maxDepth, path, sink, rng, stk, PixelScreen{x, y});
+            else
+                DirectSample(S, sink, x, y, minDepth, maxDepth, rng, stk);
+            paths++;
+        }
+        CommitOwnPixel(film, sink, lane);
+    }
+    const unsigned long long np = WaveSumU64(paths), ns = WaveSumU64(sink.splats);
+    if (lane == 0 && np) atomicAdd(counters + 0, np), atomicAdd(counters + 1, ns);
+}
+
+}  // namespace
+
+void LaunchMC(const DScene &S, const Film &film, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin, long long streamEnd,
+              uint32_t *tabScratch, unsigned long long *counters, hipStream_t s) {
+    const int nX = (S.cam.width + 15) / 16, nY = (S.cam.height + 15) / 16, nTiles = nX * nY;
+    if (streamEnd <= streamBegin) return;
+    const long long sBase = streamBegin / nTiles, sLast = (streamEnd - 1) / nTiles;
+    const int nS = (int)(sLast - sBase + 1);
+    const long long nThreads = (long long)nTiles * nS;
+    const dim3 grid((unsigned)((nThreads + 63) / 64)), block(64);
+#define LMC_MC_ARGS S, film, spp, nX, nTiles, sBase, nS, streamBegin, streamEnd, minDepth, maxDepth, tabScratch, counters
+    if (S.glossy && bidirectional) hipLaunchKernelGGL((k_mc<true, true>), grid, block, 0, s, LMC_MC_ARGS);
+    else if (S.glossy) hipLaunchKernelGGL((k_mc<true, false>), grid, block, 0, s, LMC_MC_ARGS);
+    else if (bidirectional) hipLaunchKernelGGL((k_mc<false, true>), grid, block, 0, s, LMC_MC_ARGS);
+    else
+        hipLaunchKernelGGL((k_mc<false, false>), grid, block, 0, s, LMC_MC_ARGS);
+#undef LMC_MC_ARGS
+}
+long long MCThreads(const DScene &S, long long streamBegin, long long streamEnd) {
+    const int nTiles = ((S.cam.width + 15) / 16) * ((S.cam.height + 15) / 16);
+    if (streamEnd <= streamBegin) return 0;
+    return (long long)nTiles * ((streamEnd - 1) / nTiles - streamBegin / nTiles + 1);
+}

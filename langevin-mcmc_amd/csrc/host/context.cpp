@@ -159,6 +159,8 @@ struct lmc_ctx {
     int bvhDepth = 0;
     // film
     DevBuf<float> film, directFilm;
+    DevBuf<float> mcFilm;                   // lmc_mc_render's film (the mc integrator), weighted by 1 / spp
+    DevBuf<unsigned long long> mcCounters;  // [paths traced, contributions splatted] of the last lmc_mc_render
     int world = 1, rank = 0;          // position in the job (lmc_comm_init: RCCL ranks; lmc_group_chains_init: in-process group)
     std::vector<lmc_ctx *> group;    // in-process group this context is a member of (empty / 1: none)
     bool filmReduced = false;  // the device film + weightSum already hold the all-reduced sums (lmc_film_allreduce is in place)
@@ -477,7 +479,9 @@ static void SyncOptions(lmc_ctx *c) {
     d.roughnessThreshold = o.roughnessThreshold, d.largeStepProbability = o.largeStepProbability, d.largeStepProbScale = o.largeStepProbScale;
     d.malaGN = o.malaGN, d.malaStepsize = o.malaStepsize, d.malaStdDev = o.malaStdDev, d.perturbStdDev = o.perturbStdDev;
     d.discreteStdDev = o.discreteStdDev, d.uniformMixingProbability = o.uniformMixingProbability, d.seedOffset = o.seedOffset;
-    if (o.maxDepth > MAXD || o.maxDepth < 1) throw std::runtime_error("maxdepth must be in [1, 12] on the MI355X back end");
+    if (o.maxDepth > MAXD || o.maxDepth < 1)
+        throw std::runtime_error(std::string("maxdepth must be in [1, 12] on the MI355X back end") +
+                                 (o.integrator == "mc" ? " (integrator=mc too: unbounded paths, maxdepth -1, are not served)" : ""));
     d.useLightCoord = o.useLightCoordinateSampling ? 1 : 0;
     c->S.sceneParams[0] = d.useLightCoord ? 1.0f : 0.0f;  // scene.cpp:165: the flag opens the serialized scene block the path programs read
     d.sampleCache = (o.sampleFromGlobalCache && o.mala) ? 1 : 0;  // mlt.cpp:71-73: LargeStepCache only together with mala
@@ -636,6 +640,7 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
     else if (n == "uselightcoordinatesampling") o.useLightCoordinateSampling = v != 0;
     else if (n == "largestepmultiplexed") o.largeStepMultiplexed = v != 0;
     else if (n == "samplecache") o.sampleFromGlobalCache = v != 0;
+    else if (n == "bidirectional") o.bidirectional = v != 0;  // the generator of lmc_mc_render (tests: both on one scene)
     else if (n == "max-derivatives-depth") c->maxDervDepth = (int)v;  // main.cpp:59-60
     else if (n == "timing") c->timing = v != 0;  // record per-step HIP events for lmc_step_timing / lmc_kernel_timing
     else if (n == "exp_resort") c->pendingResort = (int)v;
@@ -673,6 +678,8 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "uselightcoordinatesampling") *v = o.useLightCoordinateSampling ? 1 : 0;
     else if (n == "largestepmultiplexed") *v = o.largeStepMultiplexed ? 1 : 0;
     else if (n == "samplecache") *v = o.sampleFromGlobalCache ? 1 : 0;
+    else if (n == "bidirectional") *v = o.bidirectional ? 1 : 0;
+    else if (n == "integrator_mc") *v = o.integrator == "mc" ? 1 : 0;  // <string integrator>: "mcmc" (default) or "mc" (lmc_mc_render)
     else if (n == "bvh_quantised") *v = c->S.qnodes ? 1 : 0;            // back-end state, not a <dpt> option: the node format of the scene's hot launches ...
     else if (n == "bvh_thick_flat_share") *v = c->thickFlatShare;       // ... and the figure it was chosen by (UploadScene)
     else if (n == "resident_steps") *v = c->residentSteps;
@@ -2340,6 +2347,54 @@ static int PathTracePass(lmc_ctx *c, int directSpp, int minDepth, int maxDepth) 
     LaunchDirect(c->S, film, directSpp, minDepth, maxDepth, c->bvhDepth, !e || atoi(e) != 0, tab.p, c->stream);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipGetLastError());
+    return 0;
+    LMC_CATCH(-1)
+}
+
+// The mc integrator (PathTrace, pathtrace.cpp:14-78; device/mc.hip): stream ids [begin, end) of nTiles * spp into the MC film, cleared first.
+// Generator, depth range and seed offset are the scene's (<dpt bidirectional / mindepth / maxdepth / seedoffset>).
+int lmc_mc_render(lmc_ctx *c, int spp, long long streamBegin, long long streamEnd) {
+    LMC_TRY
+    HIP_CHECK(hipSetDevice(c->device));
+    if (spp < 1) throw std::runtime_error("lmc_mc_render: spp >= 1 expected");
+    const int W = c->S.cam.width, H = c->S.cam.height;
+    const long long nTiles = (long long)((W + 15) / 16) * ((H + 15) / 16), total = nTiles * spp;
+    if (streamEnd == -1) streamEnd = total;
+    if (streamBegin < 0 || streamBegin > streamEnd || streamEnd > total)
+        throw std::runtime_error("lmc_mc_render: stream range [" + std::to_string(streamBegin) + ", " + std::to_string(streamEnd) + ") outside [0, " +
+                                 std::to_string(total) + ")");
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (c->mcFilm.n != (size_t)W * H * 3) c->mcFilm.Alloc((size_t)W * H * 3, false);
+    if (c->mcCounters.n != 2) c->mcCounters.Alloc(2, false);
+    HIP_CHECK(hipMemsetAsync(c->mcFilm.p, 0, c->mcFilm.n * sizeof(float), c->stream));
+    HIP_CHECK(hipMemsetAsync(c->mcCounters.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const long long nThreads = MCThreads(c->S, streamBegin, streamEnd);
+    DevBuf<uint32_t> tab;  // written only by a stream that ticks (once per 2^32 draws)
+    tab.Alloc((size_t)((nThreads + 63) / 64 * 64) * 64, false);
+    Film film{c->mcFilm.p, W, H};
+    LaunchMC(c->S, film, c->scene->options.bidirectional, spp, c->S.opt.minDepth, c->S.opt.maxDepth, streamBegin, streamEnd, tab.p, c->mcCounters.p, c->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+    LMC_CATCH(-1)
+}
+int lmc_mc_read(lmc_ctx *c, float *rgb) {
+    LMC_TRY
+    if (c->mcFilm.n == 0) throw std::runtime_error("lmc_mc_read before lmc_mc_render");
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(hipMemcpy(rgb, c->mcFilm.p, c->mcFilm.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+    LMC_CATCH(-1)
+}
+int lmc_mc_stats(lmc_ctx *c, long long *out2) {
+    LMC_TRY
+    out2[0] = out2[1] = 0;
+    if (c->mcCounters.n != 2) return 0;
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    const std::vector<unsigned long long> v = c->mcCounters.Download();
+    out2[0] = (long long)v[0], out2[1] = (long long)v[1];
     return 0;
     LMC_CATCH(-1)
 }

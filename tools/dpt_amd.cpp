@@ -1,10 +1,15 @@
-// dpt_amd: the reference's process surface for the LMC path (`dpt [--seedoffset N] scene.xml ...`,
-// /root/reference/src/main.cpp:30-118) on top of the C ABI of liblmc_hip.so.  Same scene XML, same <dpt> keys, same
-// output naming (<film filename>_timeuse_<seconds>s.exr written next to the scene, mlt.cpp:208) and the same stdout
-// lines ("Average brightness:", "Elapsed time:", "Done!").  Only integrator = mcmc with mala = true (the LMC path) is
-// served; anything else is refused.  Extra flags (not in the reference): --chains N (Markov chains resident on the GPUs,
-// default: <dpt numchains>), --init-threads V (MLTInit streams, default 65536), --device D, --force-diffuse, --maxdepth D, --resident K (the
-// resident schedule, lmc_set_option "resident_steps": up to K mutations of every chain per launch once the gradient caches are frozen; H2MC
+// dpt_amd: the reference's process surface (`dpt [--seedoffset N] scene.xml ...`, main.cpp:30-118 of the reference) on top of the C
+// ABI of liblmc_hip.so.  Same scene XML, same <dpt> keys, same output naming (<film filename>_timeuse_<seconds>s.exr written next to the
+// scene, mlt.cpp:208) and the same stdout lines ("Average brightness:", "Elapsed time:", "Done!").  The scene's <string integrator> is
+// dispatched on first, as main.cpp:92-104 does:
+//   mc    PathTrace (pathtrace.cpp:14-78) through lmc_mc_render: spp samples per pixel, bidirectional or not as <dpt> says, "Elapsed time:"
+//         around the render.  The one deliberate deviation: the reference computes this film and writes nothing (pathtrace.cpp:77,
+//         main.cpp:95); dpt_amd writes it like the MLT branch does.  --seedoffset feeds the streams' seed offset (the reference's PathTrace
+//         ignores it; with the default 0 the two agree).  --gpus / --devices split the stream range into contiguous shards, one context
+//         per device, and the films are summed on the host.  The MLT-only flags (--chains, --resident, --init-threads) are ignored.
+//   mcmc  the LMC path: mala = true or h2mc = true; plain MLT (both false) is refused.
+// Extra flags (not in the reference): --chains N (Markov chains resident on the GPUs, default: <dpt numchains>), --init-threads V (MLTInit
+// streams, default 65536), --device D, --force-diffuse, --maxdepth D, --resident K (the resident schedule, lmc_set_option "resident_steps": up to K mutations of every chain per launch once the gradient caches are frozen; H2MC
 // renders stay in lock step), and
 // --gpus N (devices 0 .. N-1) / --devices a,b,.. (an explicit list; a device may appear more than once: bring-up on one GPU): the chains are
 // sharded over the listed devices as ranks of ONE job (lmc_group_*: MLTInit sharded by init stream, contiguous chain-id ranges, the gradient
@@ -15,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "lmc_abi.h"
@@ -28,11 +34,58 @@ static double Opt(lmc_ctx *ctx, const char *name) {
     return v;
 }
 
+// integrator = mc: the stream range [0, nTiles * spp) split into contiguous shards, one per context, rendered concurrently
+static int RenderMC(const std::string &filename, const std::vector<lmc_ctx *> &ctxs) {
+    lmc_ctx *ctx = ctxs[0];
+    int info[8];
+    lmc_info(ctx, info);
+    const int W = info[0], H = info[1], spp = (int)Opt(ctx, "spp"), nDev = (int)ctxs.size();
+    const long long total = (long long)((W + 15) / 16) * ((H + 15) / 16) * spp;
+    if (nDev > 1) printf("%lld sample streams sharded over %d devices\n", total, nDev);
+    std::vector<int> rc(nDev, 0);
+    std::vector<std::string> err(nDev);  // lmc_last_error is per thread
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::thread> th;
+    for (int k = 0; k < nDev; k++)
+        th.emplace_back([&, k] {
+            rc[k] = lmc_mc_render(ctxs[k], spp, total * k / nDev, total * (k + 1) / nDev);
+            if (rc[k] != 0) err[k] = lmc_last_error();
+        });
+    for (auto &t : th) t.join();
+    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int k = 0; k < nDev; k++)
+        if (rc[k] != 0) {
+            fprintf(stderr, "%s\n", err[k].c_str());
+            return 1;
+        }
+    printf("Elapsed time:%g\n", elapsed);  // pathtrace.cpp:74-75
+    std::vector<float> img((size_t)W * H * 3, 0.0f), part((size_t)W * H * 3);
+    long long paths = 0, splats = 0;
+    for (lmc_ctx *c : ctxs) {
+        long long st[2];
+        if (lmc_mc_read(c, part.data()) != 0 || lmc_mc_stats(c, st) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+        for (size_t i = 0; i < img.size(); i++) img[i] += part[i];
+        paths += st[0], splats += st[1];
+    }
+    std::string dir = filename.rfind('/') != std::string::npos ? filename.substr(0, filename.rfind('/') + 1) : "";
+    std::string out = dir + lmc_output_name(ctx) + "_timeuse_" + std::to_string(elapsed) + "s.exr";
+    if (lmc_image_write_exr(out.c_str(), img.data(), W, H) != 0) {
+        fprintf(stderr, "%s\n", lmc_last_error());
+        return 1;
+    }
+    printf("%lld paths, %lld contributions, %.1f M paths/s, wrote %s\n", paths, splats, paths / elapsed * 1e-6, out.c_str());
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc <= 1) return 0;
     printf("Langevin MCMC dpt (MI355X back end)\n");
     int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8, resident = 0;
     long long chains = 0;
+    bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
     for (int i = 1; i < argc; ++i) {
@@ -41,8 +94,8 @@ int main(int argc, char *argv[]) {
         else if (a == "--max-derivatives-depth") maxDervDepth = std::stoi(argv[++i]);  // main.cpp:59-60: techniques longer than this get isotropic proposals
         else if (a == "--compile-pathlib" || a == "--compile-bidirpathlib" || a == "--compile-bidirpathlib2") {
             printf("%s: nothing to compile, the path programs are part of liblmc_hip.so\n", a.c_str());
-        } else if (a == "--chains") chains = std::stoll(argv[++i]);
-        else if (a == "--init-threads") initThreads = std::stoi(argv[++i]);
+        } else if (a == "--chains") chains = std::stoll(argv[++i]), mltFlags = true;
+        else if (a == "--init-threads") initThreads = std::stoi(argv[++i]), mltFlags = true;
         else if (a == "--device") device = std::stoi(argv[++i]);
         else if (a == "--gpus") {
             const int n = std::stoi(argv[++i]);
@@ -58,7 +111,7 @@ int main(int argc, char *argv[]) {
             }
         } else if (a == "--force-diffuse") forceDiffuse = 1;
         else if (a == "--maxdepth") maxDepth = std::stoi(argv[++i]);
-        else if (a == "--resident") resident = std::stoi(argv[++i]);
+        else if (a == "--resident") resident = std::stoi(argv[++i]), mltFlags = true;
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -85,6 +138,14 @@ int main(int argc, char *argv[]) {
             ctxs.push_back(c);
         }
         lmc_ctx *ctx = ctxs[0];
+        if (Opt(ctx, "integrator_mc") != 0) {  // main.cpp:92-96
+            if (mltFlags) printf("--chains / --resident / --init-threads: ignored by integrator=mc\n");
+            const int rc = RenderMC(filename, ctxs);
+            for (lmc_ctx *c : ctxs) lmc_destroy(c);
+            if (rc != 0) return rc;
+            printf("Done!\n");
+            continue;
+        }
         if (Opt(ctx, "mala") == 0 && Opt(ctx, "h2mc") == 0) {
             fprintf(stderr, "dpt_amd serves the LMC path only (<dpt> integrator=mcmc with mala=true or h2mc=true)\n");
             return 1;
