@@ -263,6 +263,26 @@ int lmc_h2_gauss_probe(int n, int dim, const float *grad, const float *hess, flo
  * to obtain the bytes-per-count factors profiles/pmc_step_kernel.json applies.  Returns 0 on success. */
 int lmc_stream_probe(long long n_words, int reps);
 
+/* Checkpoint and resume (INTEGRATION.md "Checkpoint and resume"; device/checkpoint.hip).  A checkpoint is one file: a header with the fingerprint of
+ * everything the chain states depend on (a content hash of the scene's files, force_diffuse, film size, depths, seed offset, use_gradient,
+ * max-derivatives-depth and the <dpt> options the chain loop reads), the job's shape, the steps and wall seconds so far; the job-wide state (init
+ * results, gradient caches, counters, film); and one record per chain of the job in chain order -- independent of the slots the chains lived in, of
+ * the schedule that ran them and of the number of in-process members that held them.
+ * save: legal between two lmc_chains_step calls, after lmc_chains_init or a load; drains the context's streams, writes path + ".tmp" and renames
+ *       it, and changes nothing in the context.  Refused before init, on a film that already holds a reduced sum, and inside an RCCL job.
+ * load: takes the place of lmc_chains_init on a context created from the same scene and overrides with the same options set; the fingerprint is
+ *       compared field by field and a mismatch (or a wrong magic / version, or a truncated file) returns -1 with the field's name in
+ *       lmc_last_error, leaving the context as it was.  resident_steps / resident_lanes / resort_every / resort_first / overlap / timing and
+ *       LMC_RELOCATE are the loading context's own.  The chains come back in the identity layout, as after init.
+ * group calls: the same file format; a file written by one context or by a group of any size loads into one context or into a group of any size
+ *       (chains split like lmc_group_chains_init); every member receives the job-wide state, member 0 alone the film, counters and weight sum.
+ * info: host only; the header as a JSON document (lmc_scene_dump's convention: at most cap - 1 characters + NUL, returns the full length, -1 on error). */
+int lmc_checkpoint_save(lmc_ctx *ctx, const char *path);
+int lmc_checkpoint_load(lmc_ctx *ctx, const char *path);
+int lmc_group_checkpoint_save(lmc_ctx **ctxs, int n, const char *path);
+int lmc_group_checkpoint_load(lmc_ctx **ctxs, int n, const char *path);
+long long lmc_checkpoint_info(const char *path, char *json, long long cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,13 @@ def lib():
         L.lmc_comm_barrier.argtypes = [vp]
         L.lmc_host_issue_timing.argtypes = [vp, vp, vp]
         L.lmc_group_info.argtypes = [vp, ctypes.c_int, vp]
+        if hasattr(L, "lmc_checkpoint_save"):  # (an A/B library built from an older tree, LMC_LIB, has no checkpoints)
+            L.lmc_checkpoint_save.argtypes = [vp, ctypes.c_char_p]
+            L.lmc_checkpoint_load.argtypes = [vp, ctypes.c_char_p]
+            L.lmc_group_checkpoint_save.argtypes = [vp, ctypes.c_int, ctypes.c_char_p]
+            L.lmc_group_checkpoint_load.argtypes = [vp, ctypes.c_int, ctypes.c_char_p]
+            L.lmc_checkpoint_info.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_ll]
+            L.lmc_checkpoint_info.restype = c_ll
         _lib = L
     return _lib
 
@@ -154,6 +161,24 @@ class Renderer:
     def step(self, n):
         if lib().lmc_chains_step(self.h, n) != 0:
             raise RuntimeError("lmc_chains_step failed: " + _err())
+
+    def save_checkpoint(self, path):
+        """The chains, caches, counters and film as they are between two step() calls, into one file (written as path + ".tmp", then renamed);
+        changes nothing in the renderer."""
+        if lib().lmc_checkpoint_save(self.h, os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_checkpoint_save failed: " + _err())
+        return getattr(self, "normalization", None)
+
+    def load_checkpoint(self, path):
+        """Takes the place of init_chains on a renderer created from the same scene, overrides and options: the render a save_checkpoint (of a
+        Renderer or a Group of any size) wrote goes on exactly where it stopped.  Returns the normalization and sets num_chains."""
+        if lib().lmc_checkpoint_load(self.h, os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_checkpoint_load failed: " + _err())
+        self.num_chains = self.num_chains_total = checkpoint_info(path)["n_chains_total"]
+        n = ctypes.c_float()
+        lib().lmc_init_result(self.h, ctypes.byref(n), None)
+        self.normalization = n.value
+        return n.value
 
     def sync(self):
         if lib().lmc_sync(self.h) != 0:
@@ -349,6 +374,28 @@ class Group:
         if L.lmc_group_chains_step(self._arr, len(self.rens), n) != 0:
             raise RuntimeError("lmc_group_chains_step failed: " + _err())
 
+    def save_checkpoint(self, path):
+        """One file for the whole job: the members' chains in chain order, the job-wide state once, the members' films, counters and weight sums summed.
+        Save before film_reduce()."""
+        if lib().lmc_group_checkpoint_save(self._arr, len(self.rens), os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_group_checkpoint_save failed: " + _err())
+
+    def load_checkpoint(self, path):
+        """Takes the place of init_chains: the file's chains split over the members like init_chains splits them, whatever wrote the file (a Renderer,
+        a Group of another size).  Member 0 receives the film, the counters and the weight sum.  Returns the normalization."""
+        L = lib()
+        if L.lmc_group_checkpoint_load(self._arr, len(self.rens), os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_group_checkpoint_load failed: " + _err())
+        from . import sharding
+
+        total = checkpoint_info(path)["n_chains_total"]
+        for ren, (b, e) in zip(self.rens, sharding.group_ranges(total, len(self.rens))):
+            ren.num_chains, ren.num_chains_total = e - b, total
+            nn = ctypes.c_float()
+            L.lmc_init_result(ren.h, ctypes.byref(nn), None)
+            ren.normalization = nn.value
+        return self.rens[0].normalization
+
     def resident_stats(self):
         """resident_stats() of the members combined: launches, chain-steps, kernel ms and guard summed; lock steps and K of member 0 (equal on all)"""
         st = [r.resident_stats() for r in self.rens]
@@ -376,6 +423,17 @@ class Group:
 def device_count():
     """HIP devices visible to this process (0 without a GPU)."""
     return int(lib().lmc_device_count())
+
+
+def checkpoint_info(path):
+    """The header of a checkpoint file as a dict (host only): fingerprint fields, n_chains_total, samples_per_chain, steps_done, wall_seconds, sizes."""
+    import json
+
+    buf = ctypes.create_string_buffer(4096)
+    n = lib().lmc_checkpoint_info(os.fsencode(path), buf, len(buf))
+    if n < 0:
+        raise RuntimeError("lmc_checkpoint_info failed: " + _err())
+    return json.loads(buf.value.decode())
 
 
 def comm_unique_id():

@@ -141,3 +141,8 @@ void LaunchRelocateFine(const lmcd::ChainArrays &A, int maxDepth, const RelocBuf
 // dilated grid of one cache dim on the device (DCacheDim::gridStart / gridRows); buffer sizes in kernels.hip
 void LaunchBuildCacheGrid(const float *pts, int n, int dim, int G, int m, const int *coord, int *scratchStart, int *scratchCursor, int *scratchWordCount, int *tileSums,
                           uint2 *words, int *cellStart, unsigned short *idx, hipStream_t s);
+// checkpoint records (checkpoint.hip): the chains [first, first + n) of this context as n fixed-size records in chain order (read through A.slotOf), and
+// back into the slots [first, first + n) of a freshly set-up identity layout.  h2Gauss: H2Arrays::gauss of an H2MC render, nullptr otherwise
+size_t CkptRecordWords(int maxDepth, bool sampleCache, bool h2mc);
+void LaunchCkptPack(const lmcd::ChainArrays &A, int maxDepth, bool sampleCache, const float *h2Gauss, int first, int n, float *staging, hipStream_t s);
+void LaunchCkptUnpack(const lmcd::ChainArrays &A, int maxDepth, bool sampleCache, float *h2Gauss, int first, int n, const float *staging, hipStream_t s);

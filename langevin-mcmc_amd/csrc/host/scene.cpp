@@ -366,6 +366,7 @@ static TextureRef ParseTexture(ParseCtx &cx, const XmlNode &node) {
     Bitmap bm;
     bm.filename = filename;
     bool is8 = false;
+    cx.scene->sourceFiles.push_back(cx.baseDir + filename);
     bm.img = ReadImage(cx.baseDir + filename, &is8);
     bm.gamma = is8 ? 2.2f : 1.0f;
     double acc[3] = {0, 0, 0};
@@ -537,6 +538,7 @@ static void ParseShape(ParseCtx &cx, const XmlNode &node) {
     }
     Mesh mesh;
     mesh.material = material;
+    cx.scene->sourceFiles.push_back(cx.baseDir + filename);
     if (type == "serialized") LoadSerialized(cx.baseDir + filename, shapeIndex, toWorld, flipNormals, faceNormals, mesh);
     else LoadObj(cx.baseDir + filename, toWorld, flipNormals, faceNormals, mesh);
     FinishMesh(mesh);
@@ -622,6 +624,7 @@ static void ParseEmitter(ParseCtx &cx, const XmlNode &node) {
             }
         }
         L.toLight = Invert(L.toWorld);
+        cx.scene->sourceFiles.push_back(cx.baseDir + filename);
         L.image = ReadImage(cx.baseDir + filename);
         CreateEnvmapSampleInfo(L);
         S.envLight = (int)S.lights.size();
@@ -758,7 +761,9 @@ std::unique_ptr<Scene> ParseScene(const std::string &filename, const LoadOverrid
     std::string dir;
     size_t sl = filename.rfind('/');
     if (sl != std::string::npos) dir = filename.substr(0, sl + 1);
-    return ParseSceneString(ss.str(), dir, ov);
+    std::unique_ptr<Scene> scene = ParseSceneString(ss.str(), dir, ov);
+    scene->sourceFiles.insert(scene->sourceFiles.begin(), filename);
+    return scene;
 }
 
 void SerializeSceneBlock(const Scene &scene, float out[38]) {

@@ -119,6 +119,7 @@ struct Scene {
     V3 bsphereCenter{0, 0, 0};
     float bsphereRadius = 0.f;  // already x1000 (scene.cpp:40)
     std::string outputName = "image.exr";
+    std::vector<std::string> sourceFiles;  // the XML (ParseScene) and every file it pulled in, in parse order: what a checkpoint's scene hash covers
     size_t numTris() const {
         size_t n = 0;
         for (auto &m : meshes) n += m.numTris();

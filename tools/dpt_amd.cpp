@@ -15,6 +15,11 @@
 // sharded over the listed devices as ranks of ONE job (lmc_group_*: MLTInit sharded by init stream, contiguous chain-id ranges, the gradient
 // cache's pushes exchanged while it fills -- the trajectories of a single device holding all the chains), and the per-device films are summed
 // on the devices before the image is written (mlt.cpp:203-207 merges its per-thread films the same way).
+// Checkpoints (lmc_checkpoint_* / lmc_group_checkpoint_*, INTEGRATION.md "Checkpoint and resume"): --checkpoint FILE writes the render's state at the
+// end of the run, with --checkpoint-every S also every S steps; --max-steps S stops this invocation after S steps, writes the checkpoint and the
+// image of what has been rendered so far; --resume FILE skips MLTInit and continues to the scene's spp (the direct pre-pass is recomputed: it is
+// deterministic).  The _timeuse_<seconds>s suffix carries the seconds of all legs.  All of it works with --gpus / --devices.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +29,13 @@
 #include <vector>
 
 #include "lmc_abi.h"
+
+// a number of a flat JSON document (lmc_checkpoint_info)
+static double JsonNumber(const std::string &json, const char *key) {
+    const std::string k = std::string("\"") + key + "\":";
+    const size_t at = json.find(k);
+    return at == std::string::npos ? 0.0 : atof(json.c_str() + at + k.size());
+}
 
 static double Opt(lmc_ctx *ctx, const char *name) {
     double v = 0;
@@ -84,7 +96,8 @@ int main(int argc, char *argv[]) {
     if (argc <= 1) return 0;
     printf("Langevin MCMC dpt (MI355X back end)\n");
     int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8, resident = 0;
-    long long chains = 0;
+    long long chains = 0, maxSteps = -1, checkpointEvery = 0;
+    std::string checkpointPath, resumePath;
     bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -112,6 +125,10 @@ int main(int argc, char *argv[]) {
         } else if (a == "--force-diffuse") forceDiffuse = 1;
         else if (a == "--maxdepth") maxDepth = std::stoi(argv[++i]);
         else if (a == "--resident") resident = std::stoi(argv[++i]), mltFlags = true;
+        else if (a == "--checkpoint") checkpointPath = argv[++i];
+        else if (a == "--checkpoint-every") checkpointEvery = std::stoll(argv[++i]);
+        else if (a == "--max-steps") maxSteps = std::stoll(argv[++i]);
+        else if (a == "--resume") resumePath = argv[++i];
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -176,8 +193,37 @@ int main(int argc, char *argv[]) {
             numInit = 8 * numChains;
             printf("numinitsamples raised to %lld for %lld chains\n", numInit, numChains);
         }
+        if ((maxSteps >= 0 || checkpointEvery > 0) && checkpointPath.empty()) {
+            fprintf(stderr, "--max-steps / --checkpoint-every need --checkpoint FILE\n");
+            return 2;
+        }
+        auto saveCheckpoint = [&]() {
+            if ((nDev == 1 ? lmc_checkpoint_save(ctx, checkpointPath.c_str()) : lmc_group_checkpoint_save(ctxs.data(), nDev, checkpointPath.c_str())) != 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                exit(1);
+            }
+        };
+        long long stepsDone = 0;
+        double secondsBefore = 0;
         if (nDev > 1) printf("%lld chains sharded over %d devices\n", numChains, nDev);
-        if ((nDev == 1 ? lmc_chains_init(ctx, numInit, (int)numChains, initThreads, 0, (int)numChains, numSamplesPerChain, chainsNeedExtraSamples)
+        if (!resumePath.empty()) {
+            if ((nDev == 1 ? lmc_checkpoint_load(ctx, resumePath.c_str()) : lmc_group_checkpoint_load(ctxs.data(), nDev, resumePath.c_str())) != 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+            char json[4096];
+            if (lmc_checkpoint_info(resumePath.c_str(), json, sizeof(json)) < 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+            stepsDone = (long long)JsonNumber(json, "steps_done"), secondsBefore = JsonNumber(json, "wall_seconds");
+            if ((long long)JsonNumber(json, "n_chains_total") != numChains || (long long)JsonNumber(json, "samples_per_chain") != numSamplesPerChain) {
+                fprintf(stderr, "%s holds %lld chains of %lld samples each, this run asks for %lld of %lld\n", resumePath.c_str(), (long long)JsonNumber(json, "n_chains_total"),
+                        (long long)JsonNumber(json, "samples_per_chain"), numChains, numSamplesPerChain);
+                return 1;
+            }
+            printf("Resumed %s: %lld steps, %g s so far\n", resumePath.c_str(), stepsDone, secondsBefore);
+        } else if ((nDev == 1 ? lmc_chains_init(ctx, numInit, (int)numChains, initThreads, 0, (int)numChains, numSamplesPerChain, chainsNeedExtraSamples)
                        : lmc_group_chains_init(ctxs.data(), nDev, numInit, (int)numChains, initThreads, numSamplesPerChain, chainsNeedExtraSamples)) != 0) {
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
@@ -187,17 +233,28 @@ int main(int argc, char *argv[]) {
         lmc_init_result(ctx, &normalization, &nContribs);
         printf("Average brightness:%g\n", normalization);
         auto t0 = std::chrono::steady_clock::now();
-        for (long long done = 0; done < numSamplesPerChain + 1; done += 64)
-            if ((nDev == 1 ? lmc_chains_step(ctx, 64) : lmc_group_chains_step(ctxs.data(), nDev, 64)) != 0) {
+        const long long targetSteps = (numSamplesPerChain + 1 + 63) / 64 * 64;  // calls of 64 steps; a chain that has run its samples is no longer stepped
+        const long long stopAt = maxSteps >= 0 ? std::min(targetSteps, stepsDone + maxSteps) : targetSteps;
+        while (stepsDone < stopAt) {
+            long long n = std::min<long long>(64, stopAt - stepsDone);
+            if (checkpointEvery > 0) n = std::min(n, checkpointEvery - stepsDone % checkpointEvery);
+            if ((nDev == 1 ? lmc_chains_step(ctx, (int)n) : lmc_group_chains_step(ctxs.data(), nDev, (int)n)) != 0) {
                 fprintf(stderr, "%s\n", lmc_last_error());
                 return 1;
             }
+            stepsDone += n;
+            if (checkpointEvery > 0 && stepsDone % checkpointEvery == 0 && stepsDone < stopAt) saveCheckpoint();
+        }
         for (lmc_ctx *c : ctxs) lmc_sync(c);
+        if (!checkpointPath.empty()) {  // before the film merge: a merged film holds every member's share on every member
+            saveCheckpoint();
+            printf("Checkpoint after %lld of %lld steps: %s\n", stepsDone, targetSteps, checkpointPath.c_str());
+        }
         if (nDev > 1 && lmc_group_film_reduce(ctxs.data(), nDev, nullptr) != 0) {  // the per-device films summed on the devices (peer copies); timed with the loop
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
         }
-        const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        const double elapsed = secondsBefore + std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();  // all legs of the render
         printf("Elapsed time:%g\n", elapsed);
         // MergeBuffer + BufferToFilm, mlt.cpp:203-207
         std::vector<float> direct((size_t)W * H * 3), indirect((size_t)W * H * 3), img((size_t)W * H * 3);
