@@ -283,6 +283,33 @@ int lmc_group_checkpoint_save(lmc_ctx **ctxs, int n, const char *path);
 int lmc_group_checkpoint_load(lmc_ctx **ctxs, int n, const char *path);
 long long lmc_checkpoint_info(const char *path, char *json, long long cap);
 
+/* Exact film (INTEGRATION.md "Exact film"): lmc_set_option "film_exact" = 1 (default 0; 1 when the environment has LMC_FILM_EXACT=1) makes the MLT
+ * film a W*H*3 array of signed 64-bit fixed-point words added with integer atomics, so the film is a pure function of the chains' trajectories: bit-equal
+ * from run to run, across slot layouts and schedules, across members and ranks, and across a checkpoint.
+ *   conversion  q = llrint((double)v * 4294967296.0): one unit is 2^-32 of the float film's unit; the product is exact in double, one round to nearest even
+ *   range       a splat with a component |v| >= 2^30 is dropped WHOLE and counted in film_overflow (a stated deviation from the float film)
+ * Set the option BEFORE the context's first lmc_chains_init / lmc_checkpoint_load: once a context has chains it keeps its mode for life (a later
+ * lmc_chains_init does not change it).  It takes effect at that first lmc_chains_init / lmc_checkpoint_load; changing it on a context whose chains are set up is refused (-1, the context
+ * stays usable).  All members of an in-process group must have the same mode.  In exact mode
+ *   lmc_film_read         converts on the device, float(double(q) * 2^-32), and returns W*H*3 floats, un-normalised, as in float mode
+ *   lmc_film_read_fixed   the raw words (W*H*3); -1 in float mode
+ *   lmc_film_overflow     *n = splats dropped by the range rule since the film was last cleared (always 0 in float mode); per context, and after
+ *                         lmc_film_allreduce the sum over the ranks
+ *   lmc_film_clear        zeroes the words and the counter
+ *   lmc_film_device_ptr   returns the int64 buffer and its word count: the ELEMENT TYPE FOLLOWS THE MODE (float in float mode)
+ *   lmc_group_film_reduce / lmc_film_allreduce   sum the int64 words (ncclInt64): exact in any order.  ALL RANKS of a communicator must have the same
+ *                         mode: lmc_film_allreduce takes the element type and count from the local mode and does not compare them across ranks
+ *                         (the in-process group is checked; rank processes are the caller's to configure alike)
+ *   checkpoints           store the int64 film (format version 2, "film_format":"fixed64" in lmc_checkpoint_info); float-mode files are version 1,
+ *                         byte for byte as before; a file loads only into a context of its own mode
+ * The direct-lighting and mc-integrator films (lmc_direct_read, lmc_mc_read) are float in either mode. */
+int lmc_film_read_fixed(lmc_ctx *ctx, long long *out);
+int lmc_film_overflow(lmc_ctx *ctx, long long *n);
+/* test probe: n splats (screen_xy n x 2 in [0,1)^2, rgb n x 3) through the device's splat routine into a fresh W x H film, one launch of n lanes in
+ * 64-thread blocks.  exact != 0: out_fixed = the W*H*3 words, *overflow = dropped splats, out_float = the converted film; exact == 0: out_float = the
+ * float film (out_fixed must be NULL).  Any output may be NULL. */
+int lmc_film_splat_probe(int W, int H, int n, const float *screen_xy, const float *rgb, int exact, long long *out_fixed, float *out_float, long long *overflow);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,10 @@ def lib():
             L.lmc_group_checkpoint_load.argtypes = [vp, ctypes.c_int, ctypes.c_char_p]
             L.lmc_checkpoint_info.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_ll]
             L.lmc_checkpoint_info.restype = c_ll
+        if hasattr(L, "lmc_film_read_fixed"):  # (an A/B library built from an older tree, LMC_LIB, has no exact film)
+            L.lmc_film_read_fixed.argtypes = [vp, vp]
+            L.lmc_film_overflow.argtypes = [vp, vp]
+            L.lmc_film_splat_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -189,6 +193,21 @@ class Renderer:
         if lib().lmc_film_read(self.h, P(f)) != 0:
             raise RuntimeError(_err())
         return f
+
+    def film_fixed(self):
+        """Exact mode (set_option("film_exact", 1) before init_chains / load_checkpoint): the film's raw words, int64 [H, W, 3], one unit =
+        2^-32 of the float film's unit; film() is np.float32(np.float64(words) * 2.0**-32).  Raises in float mode."""
+        f = np.zeros((self.height, self.width, 3), np.int64)
+        if lib().lmc_film_read_fixed(self.h, P(f)) != 0:
+            raise RuntimeError(_err())
+        return f
+
+    def film_overflow(self):
+        """Exact mode: splats dropped because a component was 2^30 or more since the film was last cleared (0 in float mode)."""
+        n = c_ll()
+        if lib().lmc_film_overflow(self.h, ctypes.byref(n)) != 0:
+            raise RuntimeError(_err())
+        return int(n.value)
 
     # ---- multi-GPU (include/lmc_abi.h): in-library RCCL sum of the device films
     def comm_init(self, n_ranks, rank, id128):
@@ -354,8 +373,18 @@ class Group:
         self.rens = list(renderers)
         self._arr = (vp * len(self.rens))(*[r.h for r in self.rens])
 
+    def _check_film_modes(self):
+        modes = [int(r.get_option("film_exact")) for r in self.rens]
+        if len(set(modes)) > 1:
+            raise RuntimeError("Group: the members differ in film_exact (%s); a group's films are merged in one format" % modes)
+
+    def film_overflow(self):
+        """film_overflow() of the members summed (after film_reduce(): still each member's own count)"""
+        return sum(r.film_overflow() for r in self.rens)
+
     def init_chains(self, num_init, n_chains_total, init_threads, per_chain, extra=0):
         L = lib()
+        self._check_film_modes()
         L.lmc_group_chains_init.argtypes = [vp, ctypes.c_int, c_ll, ctypes.c_int, ctypes.c_int, c_ll, c_ll]
         if L.lmc_group_chains_init(self._arr, len(self.rens), num_init, n_chains_total, init_threads, per_chain, extra) != 0:
             raise RuntimeError("lmc_group_chains_init failed: " + _err())
@@ -384,6 +413,7 @@ class Group:
         """Takes the place of init_chains: the file's chains split over the members like init_chains splits them, whatever wrote the file (a Renderer,
         a Group of another size).  Member 0 receives the film, the counters and the weight sum.  Returns the normalization."""
         L = lib()
+        self._check_film_modes()
         if L.lmc_group_checkpoint_load(self._arr, len(self.rens), os.fsencode(path)) != 0:
             raise RuntimeError("lmc_group_checkpoint_load failed: " + _err())
         from . import sharding
@@ -434,6 +464,21 @@ def checkpoint_info(path):
     if n < 0:
         raise RuntimeError("lmc_checkpoint_info failed: " + _err())
     return json.loads(buf.value.decode())
+
+
+def film_splat_probe(width, height, screen_xy, rgb, exact=True):
+    """Test probe: the splats (screen_xy [n, 2] in [0, 1)^2, rgb [n, 3]) through the device's splat routine into a fresh film, one launch of n lanes in
+    64-thread blocks.  exact: returns (words int64 [H, W, 3], float view [H, W, 3], overflow count); else (None, float film, 0)."""
+    xy = np.ascontiguousarray(screen_xy, np.float32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    if len(xy) != len(c):
+        raise ValueError("film_splat_probe: screen_xy and rgb differ in length")
+    fx = np.zeros((height, width, 3), np.int64) if exact else None
+    fl = np.zeros((height, width, 3), np.float32)
+    ov = c_ll()
+    if lib().lmc_film_splat_probe(int(width), int(height), len(xy), P(xy), P(c), 1 if exact else 0, P(fx) if exact else None, P(fl), ctypes.byref(ov)) != 0:
+        raise RuntimeError("lmc_film_splat_probe failed: " + _err())
+    return fx, fl, int(ov.value)
 
 
 def comm_unique_id():

@@ -285,10 +285,35 @@ LMC_D void StoreContrib(float *base, int N, int i, const Contrib &c) {
     base[8 * (size_t)N + i] = c.ssScore;
 }
 
+// The film of a launch.  Default mode: `Film`, W*H*3 floats.  Exact mode ("film_exact"): `FilmFixed`, W*H*3 + 1 signed 64-bit words in fixed
+// point -- one unit = 2^-32 of the float film's unit -- the last of them the `film_overflow` counter.
+//   q = llrint((double)v * 4294967296.0)
+// The product is exact in double (a float times a power of two), so one round-to-nearest-even remains and it is a pure function of v: the
+// integer sum of a pixel does not depend on the order in which a launch's waves reach it.  A component with |v| >= 2^30 (FILM_FX_LIMIT) cannot be
+// represented with headroom (2^31 film units per pixel channel): the WHOLE splat is dropped and counted -- a stated deviation from the float path.
+// The mode is a TYPE on the device: every splatting kernel is compiled once per film type and the host-side launch function picks one
+// (DispatchFilm), so the float kernels hold no trace of the exact film -- a run-time branch in Splat, however the mode reached it (a second
+// pointer, a bit of H), moved the register allocator's spill decisions in the step kernels (profiles/r09_film_exact_resources.txt).  Between
+// the context and a launch function the exact film travels as a `Film` whose H carries FILM_EXACT (FilmFx); no kernel sees that bit.
+constexpr float FILM_FX_LIMIT = 1073741824.0f;  // 2^30
+constexpr double FILM_FX_SCALE = 4294967296.0;  // 2^32
+constexpr int FILM_EXACT = 1 << 30;
 struct Film {
     float *rgb;  // W*H*3
     int W, H;
 };
+struct FilmFixed {
+    unsigned long long *fx;  // W*H*3 + 1; two's complement: the unsigned add is the signed one
+    int W, H;
+};
+LMC_HD Film FilmFx(long long *fx, int W, int H) { return Film{reinterpret_cast<float *>(fx), W, H | FILM_EXACT}; }
+// host side, in a launch function: f(film) with the film under its own type
+template <class F>
+void DispatchFilm(const Film &film, F &&f) {
+    if (film.H & FILM_EXACT) f(FilmFixed{reinterpret_cast<unsigned long long *>(film.rgb), film.W, film.H & ~FILM_EXACT});
+    else
+        f(film);
+}
 // image.h:66-77: nearest pixel, drop non-finite, float atomics (hardware global_atomic_add_f32)
 LMC_D void Splat(const Film &film, V2 screenPos, V3 contrib) {
     int ix = Clampi((int)(screenPos.x * film.W), 0, film.W - 1);
@@ -298,6 +323,21 @@ LMC_D void Splat(const Film &film, V2 screenPos, V3 contrib) {
         unsafeAtomicAdd(px + 0, contrib.x);
         unsafeAtomicAdd(px + 1, contrib.y);
         unsafeAtomicAdd(px + 2, contrib.z);
+    }
+}
+// ... the same pixel rule, 64-bit integer atomics
+LMC_D void Splat(const FilmFixed &film, V2 screenPos, V3 contrib) {
+    int ix = Clampi((int)(screenPos.x * film.W), 0, film.W - 1);
+    int iy = Clampi((int)(screenPos.y * film.H), 0, film.H - 1);
+    if (AllFinite(contrib)) {
+        if (fabsf(contrib.x) >= FILM_FX_LIMIT || fabsf(contrib.y) >= FILM_FX_LIMIT || fabsf(contrib.z) >= FILM_FX_LIMIT) {
+            atomicAdd(film.fx + (size_t)film.W * film.H * 3, 1ull);
+            return;
+        }
+        unsigned long long *px = film.fx + ((size_t)iy * film.W + ix) * 3;
+        atomicAdd(px + 0, (unsigned long long)llrint((double)contrib.x * FILM_FX_SCALE));
+        atomicAdd(px + 1, (unsigned long long)llrint((double)contrib.y * FILM_FX_SCALE));
+        atomicAdd(px + 2, (unsigned long long)llrint((double)contrib.z * FILM_FX_SCALE));
     }
 }
 

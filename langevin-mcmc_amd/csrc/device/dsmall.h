@@ -404,8 +404,8 @@ struct WaveProf {
 // One plain small step of chain i.  Returns nothing; all state changes go to HBM.
 // LIGHTLESS: the caller guarantees l <= 1 (DOptions::leanLightless): the light-sub-path half of the walk, ConnectVertex and the
 // registers they hold are compiled out
-template <bool WITH_GRAD, bool LIGHTLESS = false, class Stk, class Prof>
-LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays &A, const Film &film, const StepParams &P, int i, Rng &rng,
+template <bool WITH_GRAD, bool LIGHTLESS = false, class Stk, class Prof, class FILM>
+LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays &A, const FILM &film, const StepParams &P, int i, Rng &rng,
                          const LdsView &L, Stk &stk, StepStats &st, Prof &prof, float *workBuf = nullptr, size_t workStride = 0, size_t workSlot = 0) {
     const size_t N = A.N;
     int flags = A.flags[i];

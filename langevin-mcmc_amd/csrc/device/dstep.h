@@ -294,8 +294,8 @@ LMC_D void LargeStepCacheMutate(const DScene &S, const DCache &cache, const Chai
     }
 }
 
-template <bool WITH_LARGE, bool WITH_SMALL, bool WITH_GRAD, int MUX = 0, class Stk>
-LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A, const Film &film, const StepParams &P, int i, int kind, Rng &rng,
+template <bool WITH_LARGE, bool WITH_SMALL, bool WITH_GRAD, int MUX = 0, class Stk, class FILM>
+LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A, const FILM &film, const StepParams &P, int i, int kind, Rng &rng,
                      GradWork &gw, StepStats &st, Stk &stk) {
     const size_t N = A.N;
     int flags = A.flags[i];

@@ -23,6 +23,9 @@ void LaunchTransProbe(int n, int mode, const float *x, const float *y, float *o,
 void LaunchStreamProbe(long long nWords, const float *in, float *out, hipStream_t s);
 void LaunchAddInto(float *dst, const float *src, size_t n, hipStream_t s);  // dst += src
 void LaunchAddIntoF64(double *dst, const double *src, size_t n, hipStream_t s);
+void LaunchAddIntoI64(long long *dst, const long long *src, size_t n, hipStream_t s);
+void LaunchFilmFixedToFloat(const long long *fx, float *rgb, size_t n, hipStream_t s);  // rgb[i] = float(double(fx[i]) * 2^-32)
+void LaunchFilmSplatProbe(const lmcd::Film &film, int n, const float *screenXY, const float *rgb, hipStream_t s);
 // a pipeline stage's work lists (dh2coop.h H2Bins): the counts turned into offsets, the chains of `list` scattered into the stage's N-entry array by bin
 void LaunchBinsCompact(const lmcd::H2Bins &bins, const int *list, const int *listCount, int gridBlocks, hipStream_t s);
 void LaunchSplitList(const int *list, const int *listCount, int parts, int *sub, int stride, int *subCount, int gridBlocks, hipStream_t s);

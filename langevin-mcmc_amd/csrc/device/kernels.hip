@@ -1,6 +1,8 @@
 // gfx950 kernels of the LMC hot path.  One thread = one Markov chain (or one MLT-init stream / sample);
 // launches are grid-stride ("persistent thread") loops over index lists so that large steps and small
 // steps run in separate, divergence-free launches.  Launch glue is in host/context.cpp.
+#include <type_traits>
+
 #include "dh2coop.h"
 #include "kernels.h"
 #include "upload.h"
@@ -906,6 +908,24 @@ __global__ void k_add_into(T *dst, const T *src, size_t n) {
 }
 void LaunchAddInto(float *dst, const float *src, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_add_into<float>, dim3(GridFor((long long)n, 256)), dim3(256), 0, s, dst, src, n); }
 void LaunchAddIntoF64(double *dst, const double *src, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_add_into<double>, dim3(GridFor((long long)n, 256)), dim3(256), 0, s, dst, src, n); }
+// ... and its twin for the exact film (dchain.h FilmFixed): integer sums, so the order of the members does not matter
+void LaunchAddIntoI64(long long *dst, const long long *src, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_add_into<long long>, dim3(GridFor((long long)n, 256)), dim3(256), 0, s, dst, src, n); }
+// the exact film as floats (lmc_film_read in exact mode): float(double(q) * 2^-32).  Every |q| a film can hold with headroom is below 2^63, the
+// conversion to double rounds once where |q| >= 2^53, the scaling is exact and the narrowing to float rounds once more; numpy's
+// np.float32(np.float64(q) * 2.0**-32) does the same two steps.
+__global__ void k_film_fixed_to_float(const long long *fx, float *rgb, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) rgb[i] = (float)((double)fx[i] * (1.0 / FILM_FX_SCALE));
+}
+void LaunchFilmFixedToFloat(const long long *fx, float *rgb, size_t n, hipStream_t s) { hipLaunchKernelGGL(k_film_fixed_to_float, dim3(GridFor((long long)n, 256)), dim3(256), 0, s, fx, rgb, n); }
+// test probe (lmc_film_splat_probe): one caller-given splat per lane through Splat, 64-thread blocks so that many waves contend for a pixel
+template <class FILM>
+__global__ void __launch_bounds__(64) k_film_splat_probe(FILM film, int n, const float *screenXY, const float *rgb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) Splat(film, V2{screenXY[2 * (size_t)i], screenXY[2 * (size_t)i + 1]}, V3{rgb[3 * (size_t)i], rgb[3 * (size_t)i + 1], rgb[3 * (size_t)i + 2]});
+}
+void LaunchFilmSplatProbe(const Film &film, int n, const float *screenXY, const float *rgb, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { hipLaunchKernelGGL(k_film_splat_probe<std::decay_t<decltype(f)>>, dim3((n + 63) / 64), dim3(64), 0, s, f, n, screenXY, rgb); });
+}
 // dst[0] = src[0] + .. + src[n - 1], left to right (the splat-weight sums of a group's members, in rank order: the same double on every member)
 __global__ void k_sum_f64(double *dst, const double *src, int n) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {

@@ -12,6 +12,7 @@
 #endif
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "dh2mc.h"
 #include "dpipe.h"
@@ -248,7 +249,8 @@ __global__ void __launch_bounds__(64, 2) k_h2_perturb_streamed(DScene S, ChainAr
     BlockReduceStats(st, A.counters, A.weightSum, sStats);
 }
 
-__global__ void __launch_bounds__(64) k_h2_finish(DScene S, const DCache *cache, ChainArrays A, Film film, StepParams P, H2Arrays H, const int *list, const int *listCount) {
+template <class FILM>
+__global__ void __launch_bounds__(64) k_h2_finish(DScene S, const DCache *cache, ChainArrays A, FILM film, StepParams P, H2Arrays H, const int *list, const int *listCount) {
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
     LMC_RNG_JUMP_INIT();
     StepStats st;
@@ -346,5 +348,5 @@ void LaunchH2Perturb(const DScene &S, const ChainArrays &A, const StepParams &P,
 }
 void LaunchH2Finish(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const H2Arrays &H, const int *list, const int *listCount,
                     int gridBlocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_h2_finish, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, film, P, H, list, listCount);
+    DispatchFilm(film, [&](const auto &f) { hipLaunchKernelGGL(k_h2_finish<std::decay_t<decltype(f)>>, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, f, P, H, list, listCount); });
 }

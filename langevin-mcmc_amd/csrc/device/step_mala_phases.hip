@@ -14,6 +14,8 @@
 #ifndef LMC_NO_RNG_JUMP_LDS
 #define LMC_RNG_JUMP_LDS  // drng.h: the PCG jump constants of this launch live in LDS
 #endif
+#include <type_traits>
+
 #include "dpipe.h"
 
 using namespace lmcd;
@@ -148,7 +150,8 @@ __global__ void __launch_bounds__(64, LMC_MALA_MID_WAVES) k_mala_mid(DScene S, c
     BlockReduceStats(st, A.counters, A.weightSum, sStats);
 }
 
-__global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cachePtr, ChainArrays A, Film film, StepParams P, MalaPipe M, const int *list, const int *listCount) {
+template <class FILM>
+__global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cachePtr, ChainArrays A, FILM film, StepParams P, MalaPipe M, const int *list, const int *listCount) {
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
     LMC_RNG_JUMP_INIT();
     const DCache &cache = *cachePtr;
@@ -265,5 +268,5 @@ void LaunchMalaMid(const DScene &S, const DCache *cache, const ChainArrays &A, c
 }
 void LaunchMalaFinish(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const MalaPipe &M, const int *list, const int *listCount,
                       int gridBlocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_mala_finish, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, film, P, M, list, listCount);
+    DispatchFilm(film, [&](const auto &f) { hipLaunchKernelGGL(k_mala_finish<std::decay_t<decltype(f)>>, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, f, P, M, list, listCount); });
 }

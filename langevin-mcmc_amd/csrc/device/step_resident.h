@@ -17,8 +17,8 @@ namespace lmcd {
 
 // lanes: active chains per 64-lane wave (64 / 32 / 16); the other lanes of the wave idle.  Blocks of one wave.
 // guard: [0] chain-steps run by resident launches, [1] steps that would have needed the gradient program or pushed to the cache
-template <bool GLOSSY, bool QUANT, int MUX, bool LDS_STACK>
-__global__ void __launch_bounds__(256, LMC_STEP_WAVES) k_step_resident(DScene S, const DCache *cache, ChainArrays A, Film film, StepParams P, int maxSteps, int lanes,
+template <class FILM, bool GLOSSY, bool QUANT, int MUX, bool LDS_STACK>
+__global__ void __launch_bounds__(256, LMC_STEP_WAVES) k_step_resident(DScene S, const DCache *cache, ChainArrays A, FILM film, StepParams P, int maxSteps, int lanes,
                                                                        unsigned long long *guard) {
     LMC_RNG_JUMP_INIT();
     LMC_MAT_LDS_INIT(S);
@@ -64,15 +64,15 @@ __global__ void __launch_bounds__(256, LMC_STEP_WAVES) k_step_resident(DScene S,
 
 // the instantiations of one large-step form (MUX: 0 bidirectional, 1 multiplexed, 2 LargeStepCache) for the scene's material set, node format and
 // stack need; the MUX = 0 forms are compiled in step_resident.hip, the other two in step_resident_mux.hip (the two TUs compile in parallel)
-template <int MUX>
-void LaunchResidentForm(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, int maxSteps, int lanes,
+template <int MUX, class FILM>
+void LaunchResidentFormT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, int maxSteps, int lanes,
                         unsigned long long *guard, bool glossy, int bvhStackNeed, hipStream_t s) {
     constexpr int threads = 64;  // one wave per block
     RequireJumpLdsBlock(threads);
     const int blocks = (int)((A.N + lanes - 1) / lanes);
     if (blocks <= 0 || maxSteps <= 0) return;
 #define LMC_LAUNCH_RESIDENT(G, Q, L, lds) \
-    hipLaunchKernelGGL((k_step_resident<G, Q, MUX, L>), dim3(blocks), dim3(threads), lds, s, S, cache, A, film, P, maxSteps, lanes, guard)
+    hipLaunchKernelGGL((k_step_resident<FILM, G, Q, MUX, L>), dim3(blocks), dim3(threads), lds, s, S, cache, A, film, P, maxSteps, lanes, guard)
     if (bvhStackNeed <= BVH_LDS_STACK) {  // the traversal stack in LDS, sized by the scene's own need (as the large-step launch)
         const size_t lds = (size_t)threads * ((bvhStackNeed + 7) / 8 * 8) * sizeof(int);
         // the scene's node format (host/context.cpp UploadScene); the multiplexed / cache large steps walk the exact nodes, as in lock step
@@ -87,6 +87,11 @@ void LaunchResidentForm(const DScene &S, const DCache *cache, const ChainArrays 
     // a tree deeper than the LDS stack: private stack, compiled once with the glossy code in (a Lambertian scene never takes those branches)
     LMC_LAUNCH_RESIDENT(true, false, false, 0);
 #undef LMC_LAUNCH_RESIDENT
+}
+template <int MUX>
+void LaunchResidentForm(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, int maxSteps, int lanes,
+                        unsigned long long *guard, bool glossy, int bvhStackNeed, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { LaunchResidentFormT<MUX>(S, cache, A, f, P, maxSteps, lanes, guard, glossy, bvhStackNeed, s); });
 }
 
 }  // namespace lmcd

@@ -5,7 +5,13 @@
 
 using namespace lmcd;
 
+template <class FILM>
+static void LaunchStepSmallGradT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
+                         const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, hipStream_t s) {
+    (void)glossy;
+    hipLaunchKernelGGL((k_step<FILM, false, true, true, true>), dim3(gridBlocks), dim3(256), 0, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+}
 void LaunchStepSmallGrad(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
-                         const NextLists &next, float *gradBuf, int gradStride, bool /*glossy*/, int gridBlocks, hipStream_t s) {
-    hipLaunchKernelGGL((k_step<false, true, true, true>), dim3(gridBlocks), dim3(256), 0, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+                         const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { LaunchStepSmallGradT(S, cache, A, f, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, s); });
 }

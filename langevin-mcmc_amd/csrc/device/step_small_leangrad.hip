@@ -13,11 +13,11 @@
 
 using namespace lmcd;
 
-template <bool GLOSSY>
+template <class FILM, bool GLOSSY>
 #ifndef LMC_LEANGRAD_WAVES
 #define LMC_LEANGRAD_WAVES 2  // registers for two waves per SIMD: a wave of this launch then fits beside a resident wave of the hot launch
 #endif
-__global__ void __launch_bounds__(256, LMC_LEANGRAD_WAVES) k_step_small_grad(DScene S, const DCache *cache, ChainArrays A, Film film, StepParams P, const int *list,
+__global__ void __launch_bounds__(256, LMC_LEANGRAD_WAVES) k_step_small_grad(DScene S, const DCache *cache, ChainArrays A, FILM film, StepParams P, const int *list,
                                                       const int *listCount, NextLists next, float *gradBuf, int gradStride, int stackWords) {
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
     LMC_RNG_JUMP_INIT();
@@ -40,12 +40,17 @@ __global__ void __launch_bounds__(256, LMC_LEANGRAD_WAVES) k_step_small_grad(DSc
 }
 
 // gridBlocks * blockThreads must not exceed gradStride (one serialisation slot per thread)
-void LaunchStepSmallLeanGrad(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
+template <class FILM>
+static void LaunchStepSmallLeanGradT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
                              const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed, hipStream_t s) {
     RequireJumpLdsBlock(blockThreads);
     const int stackWords = LeanStackWords(bvhStackNeed);
     const size_t ldsBytes = (size_t)blockThreads * LeanLdsWordsPerThread(stackWords) * sizeof(float);
-    if (glossy) hipLaunchKernelGGL((k_step_small_grad<true>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, stackWords);
+    if (glossy) hipLaunchKernelGGL((k_step_small_grad<FILM, true>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, stackWords);
     else
-        hipLaunchKernelGGL((k_step_small_grad<false>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, stackWords);
+        hipLaunchKernelGGL((k_step_small_grad<FILM, false>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, stackWords);
+}
+void LaunchStepSmallLeanGrad(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
+                             const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { LaunchStepSmallLeanGradT(S, cache, A, f, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, blockThreads, bvhStackNeed, s); });
 }

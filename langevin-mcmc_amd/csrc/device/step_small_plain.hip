@@ -16,7 +16,7 @@
 
 using namespace lmcd;
 
-template <bool USE_LDS_STACK, bool GLOSSY, bool PROF = false, bool LIGHTLESS = false, bool QUANT = false>
+template <class FILM, bool USE_LDS_STACK, bool GLOSSY, bool PROF = false, bool LIGHTLESS = false, bool QUANT = false>
 #ifndef LMC_LEAN_K
 #define LMC_LEAN_K 1
 #endif
@@ -29,7 +29,7 @@ template <bool USE_LDS_STACK, bool GLOSSY, bool PROF = false, bool LIGHTLESS = f
 // Lambertian one 5 % (it has no registers to give), so they stay at two.
 #define LMC_LEAN_WAVES_GLOSSY_LIGHTLESS 3
 #endif
-__global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GLOSSY_LIGHTLESS : LMC_LEAN_WAVES) k_step_small(DScene S, const DCache *cache, ChainArrays A, Film film, StepParams P, const int *list,
+__global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GLOSSY_LIGHTLESS : LMC_LEAN_WAVES) k_step_small(DScene S, const DCache *cache, ChainArrays A, FILM film, StepParams P, const int *list,
                                                     const int *listCount, NextLists next, int stackWords) {
     extern __shared__ float lds[];
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
@@ -74,14 +74,15 @@ __global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GL
     if (!LMC_EXP(P.expFlags, 8)) BlockReduceStats(st, A.counters, A.weightSum, reinterpret_cast<int *>(lds));
 }
 
-void LaunchStepSmallPlain(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
+template <class FILM>
+static void LaunchStepSmallPlainT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
                           const NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads, bool profile, hipStream_t s) {
     RequireJumpLdsBlock(blockThreads);
     const int stackWords = LeanStackWords(bvhDepth);  // bvhDepth: the tree's stack need (host/accel.cpp)
     size_t ldsBytes = (size_t)blockThreads * LeanLdsWordsPerThread(stackWords) * sizeof(float);
     if (const char *e = getenv("LMC_EXP_LDS_EXTRA")) ldsBytes += (size_t)atoi(e);  // measurement aid: lowers the occupancy without touching the code
     const bool lds = bvhDepth <= BVH_LDS_STACK;
-#define LMC_LAUNCH_SMALL(...) hipLaunchKernelGGL((k_step_small<__VA_ARGS__>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, stackWords)
+#define LMC_LAUNCH_SMALL(...) hipLaunchKernelGGL((k_step_small<FILM, __VA_ARGS__>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, stackWords)
     const bool quant = S.qnodes != nullptr && lds && !profile;  // the scene's choice (host/context.cpp UploadScene); the profiling and fallback instantiations stay on the exact nodes
     if (profile && lds && glossy) LMC_LAUNCH_SMALL(true, true, true);
     else if (profile && lds && !glossy) LMC_LAUNCH_SMALL(true, false, true);
@@ -106,4 +107,8 @@ void LaunchStepSmallPlain(const DScene &S, const DCache *cache, const ChainArray
     else
         LMC_LAUNCH_SMALL(false, true);
 #undef LMC_LAUNCH_SMALL
+}
+void LaunchStepSmallPlain(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
+                          const NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads, bool profile, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { LaunchStepSmallPlainT(S, cache, A, f, P, list, listCount, next, bvhDepth, glossy, gridBlocks, blockThreads, profile, s); });
 }

@@ -134,6 +134,7 @@ struct lmc_ctx {
     // in-process group, film merge (lmc_group_film_reduce): staging for the slices pulled from the peers + the peers' weight sums, allocated when the
     // group is set up (nothing is allocated inside the merge); events: this member's film is final / this member's slice holds the sum
     DevBuf<float> filmStage;
+    DevBuf<long long> filmStageFx;  // ... in exact mode (sized for the mode when the group is set up)
     DevBuf<double> weightStage;
     hipEvent_t filmReadyEvent = nullptr, sliceReducedEvent = nullptr, weightsCopiedEvent = nullptr;
     int groupPeerPairs = 0, groupPeerEnabled = 0, groupDevices = 0;  // ordered pairs of distinct member devices / ... with direct peer access enabled (lmc_group_info)
@@ -159,6 +160,10 @@ struct lmc_ctx {
     int bvhDepth = 0;
     // film
     DevBuf<float> film, directFilm;
+    // exact mode ("film_exact", INTEGRATION.md "Exact film"): the MLT splats go to filmFx, W*H*3 signed 64-bit fixed-point words (unit 2^-32) followed by
+    // the film_overflow counter; `film` then only receives the converted floats of lmc_film_read.  directFilm and mcFilm stay float in either mode.
+    DevBuf<long long> filmFx;
+    bool filmExact = false;
     DevBuf<float> mcFilm;                   // lmc_mc_render's film (the mc integrator), weighted by 1 / spp
     DevBuf<unsigned long long> mcCounters;  // [paths traced, contributions splatted] of the last lmc_mc_render
     int world = 1, rank = 0;          // position in the job (lmc_comm_init: RCCL ranks; lmc_group_chains_init: in-process group)
@@ -579,6 +584,7 @@ lmc_ctx *lmc_create(const lmc_scene_desc *desc) {
     if (const char *e = getenv("LMC_SORT_H2MC")) c->sortH2mc = atoi(e) != 0;
     if (const char *e = getenv("LMC_SORT_GENERIC")) c->sortGeneric = atoi(e) != 0;
     if (const char *e = getenv("LMC_GRID_DIMS")) c->gridDims = std::min(4, std::max(3, atoi(e)));
+    if (const char *e = getenv("LMC_FILM_EXACT")) c->filmExact = atoi(e) != 0;  // the default of the "film_exact" option
     if (const char *e = getenv("LMC_EXP_OUTLIER_TEST")) c->expFlags |= atoi(e) ? 128 : 0;  // tests: outlier reset after 6 / 2 adjacent rejections (dchain.h OutlierReset)
     {   // work-skipping measurement switches (dstep_params.h): compiled into -DLMC_EXP_SWITCHES builds only (scripts/build_exp.sh); the shipped library
         // refuses to run while one is set -- a number produced with work skipped must not look like any other
@@ -654,7 +660,12 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
     else if (n == "exp_resort") c->pendingResort = (int)v;
     else if (n == "resort_every") c->resortEveryOpt = std::max(0, (int)v);  // period of the full re-sort (relocate.hip); takes effect at the next lmc_chains_init; overrides LMC_RESORT_EVERY
     else if (n == "resort_first") c->resortFirstOpt = std::max(0, (int)v);
-    else if (n == "resident_steps") {  // the resident schedule (RunResident); takes effect at the next lmc_chains_step
+    else if (n == "film_exact") {  // the film's accumulator (dchain.h Film): takes effect at the next lmc_chains_init / lmc_checkpoint_load
+        if ((v != 0) != c->filmExact && c->N > 0)
+            throw std::runtime_error(std::string("film_exact: this context's chains are set up with the ") + (c->filmExact ? "fixed-point" : "float") + " film; the mode is chosen before lmc_chains_init / lmc_checkpoint_load");
+        c->filmExact = v != 0;
+        return 0;
+    } else if (n == "resident_steps") {  // the resident schedule (RunResident); takes effect at the next lmc_chains_step
         if (o.h2mc && v > 0) throw std::runtime_error("resident_steps: H2MC contexts run in lock step only (their small step is the wave-cooperative pipeline)");
         if (v < 0 || v > 1e6) throw std::runtime_error("resident_steps: K >= 0 expected (0 = lock step)");
         c->residentSteps = (int)v;
@@ -690,6 +701,7 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "integrator_mc") *v = o.integrator == "mc" ? 1 : 0;  // <string integrator>: "mcmc" (default) or "mc" (lmc_mc_render)
     else if (n == "bvh_quantised") *v = c->S.qnodes ? 1 : 0;            // back-end state, not a <dpt> option: the node format of the scene's hot launches ...
     else if (n == "bvh_thick_flat_share") *v = c->thickFlatShare;       // ... and the figure it was chosen by (UploadScene)
+    else if (n == "film_exact") *v = c->filmExact ? 1 : 0;
     else if (n == "resident_steps") *v = c->residentSteps;
     else if (n == "resident_lanes") *v = c->residentLanes;
     else if (n == "resident_guard") {  // steps of resident launches that would have needed the gradient program or pushed to the cache (must stay 0)
@@ -1316,6 +1328,9 @@ void SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     LaunchInitLists((int)N, c->lists[0][0].p, c->listCounts[0].p, s);
     HIP_CHECK(hipMemsetAsync(c->nextKind.p, NEXT_LARGE, N, s));  // ... and so does A.nextKind say, which the resident launch reads (RunResident)
     HIP_CHECK(hipMemsetAsync(c->film.p, 0, c->film.n * sizeof(float), s));
+    if (c->filmExact) c->filmFx.Alloc(c->film.n + 1);  // zeroed; the last word is the film_overflow counter
+    else
+        c->filmFx.Free();
     HIP_CHECK(hipStreamSynchronize(s));
     WarmStepLaunches(c);
     c->chainsSince = std::chrono::steady_clock::now();
@@ -1384,7 +1399,9 @@ static void GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
         c->groupDevices = (int)devs.size(), c->groupPeerPairs = pairs, c->groupPeerEnabled = enabled;
         if (n > 1) {
             const size_t slice = (c->film.n + n - 1) / n;
-            c->filmStage.Alloc(slice * (n - 1), false);
+            if (c->filmExact) c->filmStageFx.Alloc(slice * (n - 1), false), c->filmStage.Free();
+            else
+                c->filmStage.Alloc(slice * (n - 1), false), c->filmStageFx.Free();
             c->weightStage.Alloc(n, false);
         }
         for (hipEvent_t *e : {&c->filmReadyEvent, &c->sliceReducedEvent, &c->weightsCopiedEvent})
@@ -1410,6 +1427,9 @@ int lmc_group_chains_init(lmc_ctx **ctxs, int n, long long numInitSamples, int n
     std::vector<std::pair<int, int>> ranges;
     for (int r = 0; r < n; r++)
         if (g[r]->comm) throw std::runtime_error("lmc_group_chains_init: a member already belongs to an RCCL job");
+    for (int r = 1; r < n; r++)  // before anything changes: the refused contexts stay as they were
+        if (g[r]->filmExact != g[0]->filmExact)
+            throw std::runtime_error("lmc_group_chains_init: the members differ in film_exact (member 0: " + std::to_string((int)g[0]->filmExact) + ", member " + std::to_string(r) + ": " + std::to_string((int)g[r]->filmExact) + "); a group's films are merged in one format");
     for (int r = 0; r < n; r++) {
         for (lmc_ctx *peer : g[r]->group)  // leaving an earlier group: its other members must not keep a pointer to this context as a peer
             if (peer != g[r]) peer->group.clear(), peer->world = 1, peer->rank = 0;
@@ -1738,6 +1758,7 @@ StepParams MakeStepParams(const lmc_ctx *c) {
     return P;
 }
 // which large-step / generic small-step kernel the options in force select (cnt: the three list lengths on the device)
+Film StepFilm(lmc_ctx *c) { return c->filmExact ? FilmFx(c->filmFx.p, c->S.cam.width, c->S.cam.height) : Film{c->film.p, c->S.cam.width, c->S.cam.height}; }
 void LaunchLarge(lmc_ctx *c, const Film &film, const StepParams &P, int cur, const int *cnt, const NextLists &next, hipStream_t sL) {
     const bool mux = c->scene->options.largeStepMultiplexed;
     (c->S.opt.sampleCache ? LaunchStepLargeCache : mux ? LaunchStepLargeMux : LaunchStepLarge)(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][0].p, cnt + 0, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, c->largeLdsStack ? c->bvhDepth : 1 << 30, c->largeBlock, sL);
@@ -1828,7 +1849,7 @@ bool StepPhase1(lmc_ctx *c, lmc_ctx::StepEvents &ev) {
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     c->filmReduced = false;
-    Film film{c->film.p, c->S.cam.width, c->S.cam.height};
+    const Film film = StepFilm(c);
     const StepParams P = MakeStepParams(c);
     if (c->timing) {
         if (c->eventPool.empty()) {
@@ -2013,7 +2034,7 @@ void BuildNextLists(lmc_ctx *c, int nxt) {
 // inside the first mutation of a render (first step 6.5 -> 2.3 ms on a warm box; LMC_NO_WARM_LAUNCH=1 for the A/B).
 static void WarmStepLaunches(lmc_ctx *c) {
     if (getenv("LMC_NO_WARM_LAUNCH")) return;
-    Film film{c->film.p, c->S.cam.width, c->S.cam.height};
+    const Film film = StepFilm(c);
     const StepParams P = MakeStepParams(c);
     c->warmCounts.Alloc(4);  // zero-filled: three empty lists
     NextLists next{c->lists[1][0].p, c->lists[1][1].p, c->lists[1][2].p, c->listCounts[1].p};
@@ -2062,7 +2083,7 @@ void RunResident(lmc_ctx *c, int steps) {
     hipStream_t s = c->stream;
     c->filmReduced = false;
     const int K = ResidentK(c);
-    Film film{c->film.p, c->S.cam.width, c->S.cam.height};
+    const Film film = StepFilm(c);
     const StepParams P = MakeStepParams(c);
     const int mux = c->S.opt.sampleCache ? 2 : c->scene->options.largeStepMultiplexed ? 1 : 0;
     static const bool resortBetween = getenv("LMC_RESIDENT_RESORT") && atoi(getenv("LMC_RESIDENT_RESORT")) != 0;  // A/B: the full re-sort between resident launches
@@ -2274,7 +2295,9 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
         if (c->group != g) throw std::runtime_error("lmc_group_film_reduce: not the group lmc_group_chains_init set up");
         if (c->filmReduced) throw std::runtime_error("lmc_group_film_reduce: the films already hold the sum over the members; step or clear them first");
         if (c->film.n != g[0]->film.n) throw std::runtime_error("lmc_group_film_reduce: the members' films differ in size");
+        if (c->filmExact != g[0]->filmExact) throw std::runtime_error("lmc_group_film_reduce: the members differ in film_exact");
     }
+    const bool exact = g[0]->filmExact;  // int64 slices, integer adds: the sum is the same in any order
     if (out_ms)  // only so that the reported time is the merge's own: the merge is stream-ordered behind the members' steps either way
         for (lmc_ctx *c : g) {
             HIP_CHECK(hipSetDevice(c->device));
@@ -2296,9 +2319,15 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
                 if (m != k) HIP_CHECK(hipStreamWaitEvent(c->stream, g[m]->filmReadyEvent, 0));
                 HIP_CHECK(hipMemcpyPeerAsync(c->weightStage.p + m, c->device, g[m]->weightSum.p, g[m]->device, sizeof(double), c->stream));
                 if (m == k || sliceLen(k) == 0) continue;
-                float *st = c->filmStage.p + (size_t)slot * slice;
-                HIP_CHECK(hipMemcpyPeerAsync(st, c->device, g[m]->film.p + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(float), c->stream));
-                LaunchAddInto(c->film.p + (size_t)k * slice, st, sliceLen(k), c->stream);
+                if (exact) {
+                    long long *st = c->filmStageFx.p + (size_t)slot * slice;
+                    HIP_CHECK(hipMemcpyPeerAsync(st, c->device, g[m]->filmFx.p + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(long long), c->stream));
+                    LaunchAddIntoI64(c->filmFx.p + (size_t)k * slice, st, sliceLen(k), c->stream);
+                } else {
+                    float *st = c->filmStage.p + (size_t)slot * slice;
+                    HIP_CHECK(hipMemcpyPeerAsync(st, c->device, g[m]->film.p + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(float), c->stream));
+                    LaunchAddInto(c->film.p + (size_t)k * slice, st, sliceLen(k), c->stream);
+                }
                 slot++;
             }
             HIP_CHECK(hipEventRecord(c->sliceReducedEvent, c->stream));
@@ -2310,7 +2339,8 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
             for (int m = 0; m < n; m++) {
                 if (m == k) continue;
                 HIP_CHECK(hipStreamWaitEvent(c->stream, g[m]->sliceReducedEvent, 0));  // == weightsCopiedEvent of m: m has read this member's scalar
-                if (sliceLen(m)) HIP_CHECK(hipMemcpyPeerAsync(c->film.p + (size_t)m * slice, c->device, g[m]->film.p + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(float), c->stream));
+                if (sliceLen(m) && exact) HIP_CHECK(hipMemcpyPeerAsync(c->filmFx.p + (size_t)m * slice, c->device, g[m]->filmFx.p + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(long long), c->stream));
+                else if (sliceLen(m)) HIP_CHECK(hipMemcpyPeerAsync(c->film.p + (size_t)m * slice, c->device, g[m]->film.p + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(float), c->stream));
             }
             LaunchSumF64(c->weightSum.p, c->weightStage.p, n, c->stream);
         }
@@ -2337,8 +2367,31 @@ int lmc_host_issue_timing(lmc_ctx *c, double *ms, long long *steps) {
 
 int lmc_film_read(lmc_ctx *c, float *rgb) {
     LMC_TRY
+    HIP_CHECK(hipSetDevice(c->device));
+    if (c->filmFx.p) LaunchFilmFixedToFloat(c->filmFx.p, c->film.p, c->film.n, c->stream);  // exact mode: converted on the device, float(double(q) * 2^-32)
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(rgb, c->film.p, c->film.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+    LMC_CATCH(-1)
+}
+// exact mode only: the raw fixed-point words (W*H*3, unit 2^-32 of the float film's unit) / the splats dropped for a component of 2^30 or more
+int lmc_film_read_fixed(lmc_ctx *c, long long *out) {
+    LMC_TRY
+    if (!c->filmFx.p) throw std::runtime_error("lmc_film_read_fixed: this context's film is the float film (set film_exact before lmc_chains_init)");
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(hipMemcpy(out, c->filmFx.p, c->film.n * sizeof(long long), hipMemcpyDeviceToHost));
+    return 0;
+    LMC_CATCH(-1)
+}
+int lmc_film_overflow(lmc_ctx *c, long long *n) {
+    LMC_TRY
+    if (!n) throw std::runtime_error("lmc_film_overflow: n is NULL");
+    *n = 0;
+    if (!c->filmFx.p) return 0;  // the float film drops nothing
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(hipMemcpy(n, c->filmFx.p + c->film.n, sizeof(long long), hipMemcpyDeviceToHost));
     return 0;
     LMC_CATCH(-1)
 }
@@ -2514,7 +2567,10 @@ int lmc_film_allreduce(lmc_ctx *c) {
     if (c->filmReduced) throw std::runtime_error("lmc_film_allreduce: the film already holds the sum over ranks (a second in-place sum would count every rank's splats again); step or clear the film first");
     c->filmReduced = true;
     // in place on the device film, on the stream the step kernels run on: ordered after the last splat, no host staging
-    RcclCheck(GetRccl().AllReduce(c->film.p, c->film.p, c->film.n, ncclFloat32, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film)");
+    // (exact mode: the int64 words and, behind them, the overflow counter -- integer sums, the same on every rank whatever the order)
+    if (c->filmFx.p) RcclCheck(GetRccl().AllReduce(c->filmFx.p, c->filmFx.p, c->filmFx.n, ncclInt64, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film, int64)");
+    else
+        RcclCheck(GetRccl().AllReduce(c->film.p, c->film.p, c->film.n, ncclFloat32, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film)");
     // the scalars that normalise the merged image: sum of splat weights (double) -- `normalization` itself is identical on
     // every rank (each runs the same MLTInit), so it is not reduced
     RcclCheck(GetRccl().AllReduce(c->weightSum.p, c->weightSum.p, 1, ncclFloat64, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(weightSum)");
@@ -2524,12 +2580,14 @@ int lmc_film_allreduce(lmc_ctx *c) {
 
 void *lmc_film_device_ptr(lmc_ctx *c, long long *nFloats) {
     if (nFloats) *nFloats = (long long)c->film.n;
+    if (c->filmFx.p) return c->filmFx.p;  // exact mode: int64 words, the same count
     return c->film.p;
 }
 
 int lmc_film_clear(lmc_ctx *c) {
     LMC_TRY
     HIP_CHECK(hipMemsetAsync(c->film.p, 0, c->film.n * sizeof(float), c->stream));
+    if (c->filmFx.p) HIP_CHECK(hipMemsetAsync(c->filmFx.p, 0, c->filmFx.n * sizeof(long long), c->stream));  // the words and the overflow counter
     c->filmReduced = false;
     return 0;
     LMC_CATCH(-1)
@@ -2652,7 +2710,11 @@ int lmc_chain_summary(lmc_ctx *c, int which, float *out, int stride) {
 extern "C++" {
 namespace {
 constexpr char kCkptMagic[8] = {'L', 'M', 'C', 'C', 'K', 'P', 'T', '\n'};
-constexpr uint32_t kCkptVersion = 1;
+// version 1: the film section is W*H*3 floats (byte for byte what every earlier build wrote); version 2: the header's filmFormat is 1 and the film
+// section is W*H*3 signed 64-bit fixed-point words (exact mode, INTEGRATION.md "Exact film").  Float-mode renders keep writing version 1.
+constexpr uint32_t kCkptVersion = 1, kCkptVersionExact = 2;
+constexpr int32_t kFilmFloat32 = 0, kFilmFixed64 = 1;
+const char *FilmFormatName(int32_t f) { return f == kFilmFixed64 ? "fixed-point int64 (film_exact=1)" : "float32 (film_exact=0)"; }
 // Chains per chunk of the record stream (device staging -> pinned host -> file): as many as fit kCkptChunkBytes.  Neither side ever holds a second
 // copy of the population; 64 MiB is where the per-chunk costs (a launch, a copy, a stream wait) have vanished against the copy itself
 // (DESIGN.md "Checkpoint": the file is the bound, by an order of magnitude).
@@ -2663,7 +2725,7 @@ struct CkptHeader {
     // fingerprint
     uint64_t sceneHash;
     int32_t forceDiffuse, width, height, maxDepth, minDepth, seedOffset, useGradient, maxDervDepth;
-    int32_t mala, h2mc, sampleCache, useLightCoord, largeStepMultiplexed, reserved0;
+    int32_t mala, h2mc, sampleCache, useLightCoord, largeStepMultiplexed, filmFormat;  // filmFormat: kFilmFloat32 / kFilmFixed64 (the word was reserved and zero in version 1)
     float largeStepProb, largeStepScale, malaStepsize, malaGN, perturbStdDev, uniformMixProb;
     // the job's shape, progress
     int32_t nChainsTotal, initThreads;
@@ -2692,7 +2754,8 @@ CkptHeader MakeCkptHeader(lmc_ctx *c) {
     CkptHeader H;
     memset(&H, 0, sizeof(H));
     memcpy(H.magic, kCkptMagic, 8);
-    H.version = kCkptVersion, H.headerBytes = sizeof(CkptHeader);
+    H.version = c->filmExact ? kCkptVersionExact : kCkptVersion, H.headerBytes = sizeof(CkptHeader);
+    H.filmFormat = c->filmExact ? kFilmFixed64 : kFilmFloat32;
     if (!c->sceneHash) c->sceneHash = HashSceneFiles(*c->scene);
     const lmc::DptOptions &o = c->scene->options;
     H.sceneHash = c->sceneHash;
@@ -2766,8 +2829,10 @@ CkptHeader ReadCkptHeader(CkptFile &F) {
     memset(&H, 0, sizeof(H));
     if (fread(&H, 1, sizeof(H), F.f) != sizeof(H)) throw std::runtime_error("checkpoint: " + F.path + " is shorter than a checkpoint header");
     if (memcmp(H.magic, kCkptMagic, 8) != 0) throw std::runtime_error("checkpoint: " + F.path + " is not a checkpoint file (wrong magic)");
-    if (H.version != kCkptVersion || H.headerBytes != sizeof(CkptHeader))
-        throw std::runtime_error("checkpoint: " + F.path + " has format version " + std::to_string(H.version) + ", this library reads version " + std::to_string(kCkptVersion));
+    if ((H.version != kCkptVersion && H.version != kCkptVersionExact) || H.headerBytes != sizeof(CkptHeader))
+        throw std::runtime_error("checkpoint: " + F.path + " has format version " + std::to_string(H.version) + ", this library reads version " + std::to_string(kCkptVersion) + " (and " +
+                                 std::to_string(kCkptVersionExact) + ", the exact film)");
+    if (H.filmFormat != (H.version == kCkptVersionExact ? kFilmFixed64 : kFilmFloat32)) throw std::runtime_error("checkpoint: " + F.path + " has an inconsistent header (film format)");
     if (fseek(F.f, 0, SEEK_END) != 0) throw std::runtime_error("checkpoint: cannot seek in " + F.path);
     const long long len = ftell(F.f);
     if (H.nChainsTotal <= 0 || H.totalBytes != sizeof(CkptHeader) + H.jobBytes + (uint64_t)H.nChainsTotal * H.recordWords * sizeof(float))
@@ -2821,6 +2886,7 @@ void CkptSave(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
     for (lmc_ctx *c : g) {
         if (c->chainBegin != next || c->numChainsTotal != c0->numChainsTotal) throw std::runtime_error(std::string(what) + ": the contexts do not hold one job's chains in order");
         if (CkptMismatch(MakeCkptHeader(c), H)) throw std::runtime_error(std::string(what) + ": the members differ in " + CkptMismatch(MakeCkptHeader(c), H));
+        if (c->filmExact != c0->filmExact) throw std::runtime_error(std::string(what) + ": the members differ in film_exact");
         next += c->N;
     }
     if (next != c0->numChainsTotal) throw std::runtime_error(std::string(what) + ": the contexts hold " + std::to_string(next) + " of the job's " + std::to_string(c0->numChainsTotal) + " chains");
@@ -2855,17 +2921,24 @@ void CkptSave(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
     {
         std::vector<unsigned long long> counters(8, 0);
         double weightSum = 0;
-        std::vector<float> film(c0->film.n, 0.f);
+        std::vector<float> film(c0->filmExact ? 0 : c0->film.n, 0.f);
+        std::vector<long long> filmFx(c0->filmExact ? c0->film.n + 1 : 0, 0);  // exact mode: summed in int64; the film_overflow counter is the word behind the film, as on the device
         for (lmc_ctx *c : g) {  // rank order, like the film merge
             HIP_CHECK(hipSetDevice(c->device));
             const std::vector<unsigned long long> cc = c->counters.Download();
             for (int k = 0; k < 8; k++) counters[k] += cc[k];
             weightSum += c->weightSum.Download()[0];
+            if (c0->filmExact) {
+                const std::vector<long long> f = c->filmFx.Download();
+                if (f.size() != filmFx.size()) throw std::runtime_error(std::string(what) + ": the members' films differ in size");
+                for (size_t k = 0; k < filmFx.size(); k++) filmFx[k] += f[k];
+                continue;
+            }
             const std::vector<float> f = c->film.Download();
             if (f.size() != film.size()) throw std::runtime_error(std::string(what) + ": the members' films differ in size");
             for (size_t k = 0; k < f.size(); k++) film[k] += f[k];
         }
-        put(counters.data(), 64), put(&weightSum, 8), put(film.data(), film.size() * 4);
+        put(counters.data(), 64), put(&weightSum, 8), put(film.data(), film.size() * 4), put(filmFx.data(), filmFx.size() * 8);
     }
     H.jobBytes = job.size();
     H.totalBytes = sizeof(CkptHeader) + H.jobBytes + (uint64_t)H.nChainsTotal * H.recordWords * sizeof(float);
@@ -2926,8 +2999,12 @@ void CkptLoad(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
     CkptFile F;
     F.Open(path, "rb");
     const CkptHeader H = ReadCkptHeader(F);
-    for (lmc_ctx *c : g)
+    for (lmc_ctx *c : g) {
         if (const char *field = CkptMismatch(H, MakeCkptHeader(c))) throw std::runtime_error(std::string(what) + ": " + path + " was written for another render: '" + field + "' differs");
+        if (H.filmFormat != (c->filmExact ? kFilmFixed64 : kFilmFloat32))
+            throw std::runtime_error(std::string(what) + ": " + path + " holds a " + FilmFormatName(H.filmFormat) + " film, this context's film is " + FilmFormatName(c->filmExact ? kFilmFixed64 : kFilmFloat32) +
+                                     "; set the film_exact option to the file's mode before loading");
+    }
     if ((size_t)H.nChainsTotal < g.size()) throw std::runtime_error(std::string(what) + ": fewer chains than members");
     // ---- the job-wide state, on the host (a few MB); everything up to here has left the contexts as they were
     std::vector<char> job(H.jobBytes);
@@ -2962,8 +3039,11 @@ void CkptLoad(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
     }
     std::vector<unsigned long long> counters(8);
     double weightSum = 0;
-    std::vector<float> film(H.filmWords);
+    const bool exact = H.filmFormat == kFilmFixed64;
+    std::vector<float> film(exact ? 0 : H.filmWords);
+    std::vector<long long> filmFx(exact ? (size_t)H.filmWords + 1 : 0);
     get(counters.data(), 64), get(&weightSum, 8), get(film.data(), film.size() * 4);
+    if (exact) get(filmFx.data(), filmFx.size() * 8);  // the words, then the film_overflow counter
     // the kd-trees of the dims the file holds ready: rebuilt from the rows by the code that built them (deterministic), once for all members
     lmc::KdTreeResult trees[CACHE_SLOTS];
     for (int sl = 0; sl < CACHE_SLOTS; sl++)
@@ -3020,7 +3100,9 @@ void CkptLoad(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
             if (r == 0) {  // the film, the counters and the weight sum go to member 0 alone: the film merge stays a sum
                 HIP_CHECK(hipMemcpy(c->counters.p, counters.data(), 64, hipMemcpyHostToDevice));
                 HIP_CHECK(hipMemcpy(c->weightSum.p, &weightSum, 8, hipMemcpyHostToDevice));
-                HIP_CHECK(hipMemcpy(c->film.p, film.data(), film.size() * 4, hipMemcpyHostToDevice));
+                if (exact) HIP_CHECK(hipMemcpy(c->filmFx.p, filmFx.data(), filmFx.size() * 8, hipMemcpyHostToDevice));
+                else
+                    HIP_CHECK(hipMemcpy(c->film.p, film.data(), film.size() * 4, hipMemcpyHostToDevice));
             }
             // the records of this member's chains
             const int chunk = (int)std::min<size_t>((size_t)c->N, std::max<size_t>(1024, kCkptChunkBytes / recBytes));
@@ -3107,11 +3189,11 @@ long long lmc_checkpoint_info(const char *path, char *out, long long cap) {
     const CkptHeader H = ReadCkptHeader(F);
     char buf[2048];
     snprintf(buf, sizeof(buf),
-             "{\"version\":%u,\"scene_hash\":\"%016llx\",\"force_diffuse\":%d,\"width\":%d,\"height\":%d,\"maxdepth\":%d,\"mindepth\":%d,\"seedoffset\":%d,\"use_gradient\":%d,"
+             "{\"version\":%u,\"film_format\":\"%s\",\"scene_hash\":\"%016llx\",\"force_diffuse\":%d,\"width\":%d,\"height\":%d,\"maxdepth\":%d,\"mindepth\":%d,\"seedoffset\":%d,\"use_gradient\":%d,"
              "\"max-derivatives-depth\":%d,\"mala\":%d,\"h2mc\":%d,\"samplecache\":%d,\"uselightcoordinatesampling\":%d,\"largestepmultiplexed\":%d,\"largestepprob\":%.9g,"
              "\"largestepscale\":%.9g,\"mala-stepsize\":%.9g,\"mala-gn\":%.9g,\"perturbstddev\":%.9g,\"uniformmixprob\":%.9g,\"n_chains_total\":%d,\"samples_per_chain\":%lld,"
              "\"chains_need_extra\":%lld,\"num_init_samples\":%lld,\"init_threads\":%d,\"steps_done\":%lld,\"wall_seconds\":%.9g,\"record_bytes\":%u,\"job_bytes\":%llu,\"total_bytes\":%llu}",
-             H.version, (unsigned long long)H.sceneHash, H.forceDiffuse, H.width, H.height, H.maxDepth, H.minDepth, H.seedOffset, H.useGradient, H.maxDervDepth, H.mala, H.h2mc, H.sampleCache,
+             H.version, H.filmFormat == kFilmFixed64 ? "fixed64" : "float32", (unsigned long long)H.sceneHash, H.forceDiffuse, H.width, H.height, H.maxDepth, H.minDepth, H.seedOffset, H.useGradient, H.maxDervDepth, H.mala, H.h2mc, H.sampleCache,
              H.useLightCoord, H.largeStepMultiplexed, H.largeStepProb, H.largeStepScale, H.malaStepsize, H.malaGN, H.perturbStdDev, H.uniformMixProb, H.nChainsTotal, (long long)H.samplesPerChain,
              (long long)H.chainsNeedExtra, (long long)H.numInitSamples, H.initThreads, (long long)H.stepsDone, H.wallSeconds, H.recordWords * 4u, (unsigned long long)H.jobBytes,
              (unsigned long long)H.totalBytes);
@@ -3285,6 +3367,35 @@ int lmc_kd_probe(int dim, int npts, const float *pts, int nq, const float *q, fl
 // parity probe: the rows of one cache dim as they stand (pss: PSS_MAX_SIZE x dim, weight: PSS_MAX_SIZE, extra: PSS_MAX_SIZE x
 // CACHE_ROW_EXTRA = every row's DPath words followed by its Contrib words, only with `samplecache`; any pointer may be NULL).
 // Returns the number of rows filled, -1 on error.
+// test probe: n caller-given splats through the device's Splat (dchain.h) into a fresh W x H film, one launch of n lanes in 64-thread blocks.
+// exact != 0: out_fixed receives the W*H*3 fixed-point words, *overflow the dropped splats; out_float the film as lmc_film_read returns it
+// (exact: converted from the words on the device).  Any of the three outputs may be NULL.
+int lmc_film_splat_probe(int W, int H, int n, const float *screen_xy, const float *rgb, int exact, long long *out_fixed, float *out_float, long long *overflow) {
+    LMC_TRY
+    EnsureDevice(0);
+    if (W <= 0 || H <= 0 || n < 0 || (long long)W * H > (1ll << 26)) throw std::runtime_error("lmc_film_splat_probe: bad film size or splat count");
+    const size_t words = (size_t)W * H * 3;
+    DevBuf<float> dXY, dRGB, dFilm;
+    DevBuf<long long> dFx;
+    dXY.Upload(screen_xy, (size_t)n * 2), dRGB.Upload(rgb, (size_t)n * 3), dFilm.Alloc(words);
+    if (exact) dFx.Alloc(words + 1);
+    if (n > 0) LaunchFilmSplatProbe(exact ? FilmFx(dFx.p, W, H) : Film{dFilm.p, W, H}, n, dXY.p, dRGB.p, 0);
+    if (exact) LaunchFilmFixedToFloat(dFx.p, dFilm.p, words, 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (out_float) HIP_CHECK(hipMemcpy(out_float, dFilm.p, words * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_fixed) {
+        if (!exact) throw std::runtime_error("lmc_film_splat_probe: the fixed-point words exist in exact mode only");
+        HIP_CHECK(hipMemcpy(out_fixed, dFx.p, words * sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    if (overflow) {
+        *overflow = 0;
+        if (exact) HIP_CHECK(hipMemcpy(overflow, dFx.p + words, sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    return 0;
+    LMC_CATCH(-1)
+}
+
 int lmc_cache_rows(lmc_ctx *c, int dim, float *pss, float *weight, float *extra) {
     LMC_TRY
     HIP_CHECK(hipSetDevice(c->device));

@@ -19,6 +19,10 @@
 // end of the run, with --checkpoint-every S also every S steps; --max-steps S stops this invocation after S steps, writes the checkpoint and the
 // image of what has been rendered so far; --resume FILE skips MLTInit and continues to the scene's spp (the direct pre-pass is recomputed: it is
 // deterministic).  The _timeuse_<seconds>s suffix carries the seconds of all legs.  All of it works with --gpus / --devices.
+// --exact-film (lmc_set_option "film_exact", INTEGRATION.md "Exact film"): the MLT film is accumulated in 64-bit fixed point, so the written image does
+// not depend on the order of the splats -- the same bytes from run to run, for any --gpus / --devices, with or without --resident, and across
+// --checkpoint / --resume.  A resume takes the mode from the file; --exact-film on a float-film checkpoint is an error.  The EXR is produced from the
+// converted float film exactly as in float mode.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -98,6 +102,7 @@ int main(int argc, char *argv[]) {
     int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8, resident = 0;
     long long chains = 0, maxSteps = -1, checkpointEvery = 0;
     std::string checkpointPath, resumePath;
+    bool exactFilm = false;
     bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -129,6 +134,7 @@ int main(int argc, char *argv[]) {
         else if (a == "--checkpoint-every") checkpointEvery = std::stoll(argv[++i]);
         else if (a == "--max-steps") maxSteps = std::stoll(argv[++i]);
         else if (a == "--resume") resumePath = argv[++i];
+        else if (a == "--exact-film") exactFilm = true;
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -174,6 +180,26 @@ int main(int argc, char *argv[]) {
                     fprintf(stderr, "%s\n", lmc_last_error());
                     return 1;
                 }
+        int filmExact = exactFilm ? 1 : (int)Opt(ctx, "film_exact");  // (without the flag: the library's default, LMC_FILM_EXACT)
+        if (!resumePath.empty()) {  // a resume takes the film's mode from the file
+            char json[4096];
+            if (lmc_checkpoint_info(resumePath.c_str(), json, sizeof(json)) < 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+            const int fileExact = strstr(json, "\"film_format\":\"fixed64\"") != nullptr;
+            if (exactFilm && !fileExact) {
+                fprintf(stderr, "--exact-film: %s holds a float film; a render keeps the film mode it was started with\n", resumePath.c_str());
+                return 2;
+            }
+            filmExact = fileExact;
+        }
+        for (lmc_ctx *c : ctxs)
+            if (lmc_set_option(c, "film_exact", filmExact) != 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+        if (filmExact) printf("Exact film: 64-bit fixed-point accumulation\n");
         int info[8];
         lmc_info(ctx, info);
         const int W = info[0], H = info[1];
@@ -268,13 +294,16 @@ int main(int argc, char *argv[]) {
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
         }
-        long long mutations = 0;
+        long long mutations = 0, dropped = 0;
         for (lmc_ctx *c : ctxs) {
-            long long st[8];
+            long long st[8], ov = 0;
             double ws = 0;
             lmc_stats(c, st, &ws);
             mutations += st[0];
+            lmc_film_overflow(c, &ov);
+            dropped += ov;
         }
+        if (dropped > 0) printf("Exact film: %lld splats with a component of 2^30 or more were dropped\n", dropped);
         printf("%lld mutations, %.1f M mutations/s, wrote %s\n", mutations, mutations / elapsed * 1e-6, out.c_str());
         for (lmc_ctx *c : ctxs) lmc_destroy(c);
         printf("Done!\n");
