@@ -247,6 +247,16 @@ int lmc_prof_read(lmc_ctx *ctx, unsigned long long *out16);
 int lmc_cache_grid_check(lmc_ctx *ctx, int dim);
 /* the lean kernel's existence test in front of the cache query, evaluated on the host: out[i] = 1 iff a cache point lies within the radius */
 int lmc_cache_filter_probe(int dim, int npts, const float *pts, int nq, const float *q, int *out);
+/* test probe, evaluated on the device: the lean small step's own cache look-up (re-use test, existence grid, candidate count, one-match shortcut,
+ * count-limited search, inverse-distance blend, ComputeGaussian) on caller-given cache rows (npts <= 3000 x dim: pts, v1, v2; dim 6, 8, 10 or 12) and
+ * one chain state per query (q, last_pss, ch_v1, ch_v2: nq x dim; queried, ss_score: nq).  grid_m 3 or 4; chosen_coords 0 = the grid over the leading
+ * coordinates, 1 = over the ones the renderer would pick; device_grid 0 = the host's grid build, 1 = the device's.
+ * out_int nq x 10 = [branch (0 isotropic, 1 re-use, 2 blend), matches, their rows in search order (5, -1 = none), cache-query and cache-hit counter
+ * increments, hit of the generic kernel's query], out_w nq x 5 blend weights, out_chain nq x 3 x dim = chain v1, v2, last_pss afterwards,
+ * out_gauss nq x (3 dim + 1) = mean, covL, invCov, logDet, out_generic nq x 2 x dim = v1, v2 of the generic kernel's query (zeros on a miss) */
+int lmc_lean_query_probe(int dim, int npts, const float *pts, const float *v1, const float *v2, float mala_stepsize, float mala_stddev, int grid_m,
+                         int chosen_coords, int device_grid, int nq, const float *q, const int *queried, const float *last_pss, const float *ch_v1,
+                         const float *ch_v2, const float *ss_score, int *out_int, float *out_w, float *out_chain, float *out_gauss, float *out_generic);
 /* ComputeGaussian (mala.cpp:7-52) + GaussianLogPdf (gaussian.cpp:24-36): out n x (3*dim+2) */
 int lmc_gauss_probe(int n, int dim, const float *v1, const float *M, float ss, float shk, const float *sc, const float *offset, float *out);
 /* Parity probes of the H2MC step's own launches (device/h2hess.hip, h2gauss.hip; reference: the evaluate_path_bidir_<c>_<l>_static_derv

@@ -84,6 +84,7 @@ def lib():
         L.lmc_occluded.argtypes = [vp, ctypes.c_int, vp, vp]
         L.lmc_rng_probe.argtypes = [ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, vp]
         L.lmc_kd_probe.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float, ctypes.c_int, vp, vp, vp]
+        L.lmc_lean_query_probe.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [vp] * 11
         L.lmc_gauss_probe.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp]
         L.lmc_comm_unique_id.argtypes = [vp]
         L.lmc_comm_init.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]

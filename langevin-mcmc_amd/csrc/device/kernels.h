@@ -32,6 +32,16 @@ void LaunchSplitList(const int *list, const int *listCount, int parts, int *sub,
 void LaunchSumF64(double *dst, const double *src, int n, hipStream_t s);  // dst[0] = sum of src[0 .. n), left to right
 void LaunchTrace(const lmcd::DScene &S, int n, const float *rays, int *prim, float *t, int anyHit, hipStream_t s);
 void LaunchKdProbe(const lmcd::DCacheDim &C, int dim, int nq, const float *q, float radiusSq, int knn, int *outN, int *outIdx, float *outDist, hipStream_t s);
+// test probe of the lean small step's cache look-up (query_probe.hip): per query i, ints[i * LEAN_PROBE_INTS ..] = [VSource mode, nMatches, idx[5] (-1: none),
+// cacheQueries, cacheHits increments, hit of the generic CacheQuery], w[i * 5 ..] the blend weights, gauss[i * (3 dim + 1) ..] = mean, covL, invCov of
+// every dimension and logDet, generic[i * 2 dim ..] = v1, v2 of the generic CacheQuery (zeros on a miss).  A: stand-in chain arrays of N = nq.
+constexpr int LEAN_PROBE_INTS = 10;
+struct LeanQueryProbeOut {
+    int *ints;
+    float *w, *gauss, *generic;
+};
+void LaunchLeanQueryProbe(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::StepParams &P, int dim, int nq, const float *q,
+                          const int *queried, const float *ssScore, const LeanQueryProbeOut &out, hipStream_t s);
 void LaunchGaussProbe(int n, int dim, const float *v1, const float *M, float ss, float shk, const float *sc, const float *offset, float *out, hipStream_t s);
 void LaunchGradBatch(int c, int l, int n, const float *primarySoA, const float *scene, const float *vertSoA, float *logLum, float *gradSoA, int wantGrad,
                      hipStream_t s);

@@ -622,10 +622,11 @@ CacheGrid BuildCacheGrid(const float *pts, int n, int dim, int m, const int *coo
     };
     for (int i = 0; i < n; i++) forNeighbours(pts + (size_t)i * dim, [&](int cell) { g.start[cell + 1]++; });
     for (size_t c = 0; c < cells; c++) g.start[c + 1] += g.start[c];
-    g.rows.resize((size_t)g.start[cells] * dim);
+    g.rows.resize((size_t)g.start[cells] * dim), g.rowIdx.resize((size_t)g.start[cells]);
     std::vector<int> cursor(g.start.begin(), g.start.end() - 1);
     for (int i = 0; i < n; i++)
         forNeighbours(pts + (size_t)i * dim, [&](int cell) {
+            g.rowIdx[cursor[cell]] = i;
             std::copy(pts + (size_t)i * dim, pts + (size_t)(i + 1) * dim, g.rows.begin() + (size_t)cursor[cell]++ * dim);
         });
     return g;

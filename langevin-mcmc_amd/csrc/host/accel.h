@@ -62,6 +62,7 @@ struct CacheGrid {
     int coord[4] = {0, 1, 2, 3};
     std::vector<int> start;
     std::vector<float> rows;
+    std::vector<int> rowIdx;  // rows[j] is a copy of point rowIdx[j]
     bool Exists(const float *q, int dim) const;  // the kernel's test, on the host
 };
 CacheGrid BuildCacheGrid(const float *pts, int n, int dim, int m, const int *coord = nullptr);  // coord == nullptr: ChooseGridCoords

@@ -3631,6 +3631,93 @@ int lmc_cache_filter_probe(int dim, int npts, const float *pts, int nq, const fl
     return 0;
     LMC_CATCH(-1)
 }
+// test probe (device/query_probe.hip): the lean small step's cache look-up on caller-given cache rows and chain states, next to the generic CacheQuery.
+// The kd-tree is the host build (as lmc_kd_probe's); the existence grid of rank grid_m lies over the leading coordinates or the ones ChooseGridCoords
+// picks, and is built by lmc::BuildCacheGrid on the host (converted to the compact layout) or by LaunchBuildCacheGrid on the device.
+int lmc_lean_query_probe(int dim, int npts, const float *pts, const float *v1, const float *v2, float malaStepsize, float malaStdDev, int gridM, int chosenCoords,
+                         int deviceGrid, int nq, const float *q, const int *queried, const float *lastPss, const float *chV1, const float *chV2, const float *ssScore,
+                         int *outInt, float *outW, float *outChain, float *outGauss, float *outGeneric) {
+    LMC_TRY
+    EnsureDevice(0);
+    if (dim < 6 || dim > PSS_MAX_LENGTH || (dim & 1) || npts < 1 || npts > PSS_MAX_SIZE || nq < 1 || gridM < 3 || gridM > 4)
+        throw std::runtime_error("lmc_lean_query_probe: bad arguments");
+    lmc::KdTreeResult t = lmc::BuildKdTree(pts, npts, dim);
+    if (t.depth >= KD_STACK || t.nodes.size() > KD_MAX_NODES) throw std::runtime_error("lmc_lean_query_probe: kd-tree deeper or larger than the search accepts");
+    DevBuf<KdNode> dN;
+    DevBuf<int> dV;
+    DevBuf<float> dP, dV1, dV2;
+    const size_t rowWords = (size_t)npts * dim;
+    dN.Upload(t.nodes), dV.Upload(t.vind), dP.Upload(pts, rowWords), dV1.Upload(v1, rowWords), dV2.Upload(v2, rowWords);
+    std::vector<DCache> cacheHost(1);
+    memset(cacheHost.data(), 0, sizeof(DCache));
+    DCacheDim &C = cacheHost[0].d[dim];
+    C.ready = 1, C.nodes = dN.p, C.vind = dV.p, C.pts = dP.p, C.v1 = dV1.p, C.v2 = dV2.p;
+    for (int k = 0; k < dim; k++) C.rootLow[k] = t.rootLow[k], C.rootHigh[k] = t.rootHigh[k];
+    // the existence grid
+    const int G = CacheGridG(dim), m = std::min(gridM, dim);
+    C.gridG = G, C.gridM = m;
+    for (int k = 0; k < 4; k++) C.gridCoord[k] = k;
+    if (chosenCoords) lmc::ChooseGridCoords(pts, npts, dim, m, C.gridCoord);
+    size_t cells = 1, nbrs = 1;
+    for (int k = 0; k < m; k++) cells *= G, nbrs *= 3;
+    const size_t nWords = (cells + 31) / 32;
+    DevBuf<uint2> dWords;
+    DevBuf<int> dCellStart, sStart, sCursor, sWordCount, sTiles;
+    DevBuf<unsigned short> dIdx;
+    if (deviceGrid) {
+        dWords.Alloc(nWords), dCellStart.Alloc(std::min(cells, (size_t)npts * nbrs) + 1), dIdx.Alloc((size_t)npts * nbrs);
+        sStart.Alloc(cells + 1), sCursor.Alloc(cells), sWordCount.Alloc(nWords), sTiles.Alloc((cells + 1) / 2048 + 2);
+        LaunchBuildCacheGrid(dP.p, npts, dim, G, m, C.gridCoord, sStart.p, sCursor.p, sWordCount.p, sTiles.p, dWords.p, dCellStart.p, dIdx.p, 0);
+        HIP_CHECK(hipGetLastError());
+    } else {
+        lmc::CacheGrid g = lmc::BuildCacheGrid(pts, npts, dim, m, C.gridCoord);
+        std::vector<uint2> words(nWords, uint2{0u, 0u});
+        std::vector<int> cellStart;
+        std::vector<unsigned short> idx(g.rowIdx.begin(), g.rowIdx.end());
+        for (size_t cell = 0; cell < cells; cell++) {
+            if ((cell & 31) == 0) words[cell >> 5].y = (unsigned)cellStart.size();
+            if (g.start[cell + 1] > g.start[cell]) words[cell >> 5].x |= 1u << (cell & 31), cellStart.push_back(g.start[cell]);
+        }
+        cellStart.push_back(g.start[cells]);
+        dWords.Upload(words), dCellStart.Upload(cellStart), dIdx.Upload(idx);
+    }
+    C.gridWords = dWords.p, C.gridCellStart = dCellStart.p, C.gridIdx = dIdx.p;
+    DevBuf<DCache> dCache;
+    dCache.Upload(cacheHost);
+    // the stand-in chain arrays ([word][chain], N = nq) and the queries
+    auto soa = [&](const float *rows) {
+        std::vector<float> v((size_t)dim * nq);
+        for (int i = 0; i < nq; i++)
+            for (int k = 0; k < dim; k++) v[(size_t)k * nq + i] = rows[(size_t)i * dim + k];
+        return v;
+    };
+    DevBuf<float> aV1, aV2, aLast, aWeight, dQ, dSs, oW, oGauss, oGeneric;
+    DevBuf<int> dQueried, oInt;
+    aV1.Upload(soa(chV1)), aV2.Upload(soa(chV2)), aLast.Upload(soa(lastPss)), aWeight.Alloc(nq);
+    dQ.Upload(q, (size_t)nq * dim), dSs.Upload(ssScore, nq), dQueried.Upload(queried, nq);
+    oInt.Alloc((size_t)nq * LEAN_PROBE_INTS), oW.Alloc((size_t)nq * 5), oGauss.Alloc((size_t)nq * (3 * dim + 1)), oGeneric.Alloc((size_t)nq * 2 * dim);
+    ChainArrays A;
+    memset(&A, 0, sizeof(A));
+    A.N = nq, A.chV1 = aV1.p, A.chV2 = aV2.p, A.chLastPss = aLast.p, A.pathWeight = aWeight.p;
+    std::vector<DScene> S(1);
+    memset(S.data(), 0, sizeof(DScene));
+    S[0].opt.malaStepsize = malaStepsize, S[0].opt.malaStdDev = malaStdDev;
+    StepParams P;
+    memset(&P, 0, sizeof(P));
+    LaunchLeanQueryProbe(S[0], dCache.p, A, P, dim, nq, dQ.p, dQueried.p, dSs.p, LeanQueryProbeOut{oInt.p, oW.p, oGauss.p, oGeneric.p}, 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(outInt, oInt.p, oInt.n * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(outW, oW.p, oW.n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(outGauss, oGauss.p, oGauss.n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(outGeneric, oGeneric.p, oGeneric.n * sizeof(float), hipMemcpyDeviceToHost));
+    const std::vector<float> after[3] = {aV1.Download(), aV2.Download(), aLast.Download()};
+    for (int i = 0; i < nq; i++)
+        for (int a = 0; a < 3; a++)
+            for (int k = 0; k < dim; k++) outChain[((size_t)i * 3 + a) * dim + k] = after[a][(size_t)k * nq + i];
+    return 0;
+    LMC_CATCH(-1)
+}
 int lmc_gauss_probe(int n, int dim, const float *v1, const float *M, float ss, float shk, const float *sc, const float *offset, float *out) {
     LMC_TRY
     EnsureDevice(0);

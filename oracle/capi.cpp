@@ -408,6 +408,44 @@ int orc_kd_query(int dim, int npts, const float *pts, int nq, const float *q, fl
     }
     return 0;
 }
+// The cache-ready branch of InitGaussianFor (mlt.cpp CacheReadyGaussian) on caller-given cache rows (npts x dim: pts, v1, v2) and one chain state per query:
+// q = the state's primary sample, queried / lastPss / chV1 / chV2 = chain->queried, last_pss, v1, v2 before the call (nq x dim), ssScore[nq].
+// outInt nq x 9 = [branch (CacheBranch), matches, their row indices in search order (5, -1 = none), cacheQueries and cacheHits increments],
+// outW nq x 5 = the blend weights, outChain nq x 3 x dim = chain->v1, v2, last_pss afterwards, outGauss nq x (3 dim + 1) = mean, covL, invCov, logDet
+int orc_cache_gaussian(int dim, int npts, const float *pts, const float *v1, const float *v2, float malaStepsize, float malaStdDev, int nq, const float *q,
+                       const int *queried, const float *lastPss, const float *chV1, const float *chV2, const float *ssScore, int *outInt, float *outW,
+                       float *outChain, float *outGauss) {
+    if (dim < PSS_MIN_LENGTH || dim > PSS_MAX_LENGTH || npts < 1 || npts > PSS_MAX_SIZE) return -1;
+    CacheDim cd;
+    cd.dim = dim;
+    cd.pss.assign(pts, pts + (size_t)npts * dim), cd.v1.assign(v1, v1 + (size_t)npts * dim), cd.v2.assign(v2, v2 + (size_t)npts * dim);
+    cd.tree.Build(cd.pss.data(), npts, dim);
+    cd.is_ready = true;
+    const int maxdim = 16;  // 2 * maxDepth of the chain vectors; only the first dim words are read
+    for (int i = 0; i < nq; i++) {
+        Chain chain;
+        for (std::vector<Float> *v : {&chain.M, &chain.pss, &chain.last_pss, &chain.v1, &chain.v2}) v->assign(maxdim, Float(0.0));
+        for (int k = 0; k < dim; k++) {
+            const size_t o = (size_t)i * dim + k;
+            chain.pss[k] = q[o], chain.last_pss[k] = lastPss[o], chain.v1[k] = chV1[o], chain.v2[k] = chV2[o];
+        }
+        chain.buffered = true, chain.queried = queried[i] != 0, chain.ss = malaStepsize;
+        StepStats st;
+        Gaussian g;
+        CacheDim::Matches m;
+        const CacheBranch b = CacheReadyGaussian(cd, chain, dim, malaStdDev, ssScore[i], g, st, &m);
+        int *oi = outInt + (size_t)i * 9;
+        oi[0] = (int)b, oi[1] = m.n, oi[7] = (int)st.cacheQueries, oi[8] = (int)st.cacheHits;
+        for (int k = 0; k < 5; k++) oi[2 + k] = k < m.n ? m.idx[k] : -1, outW[(size_t)i * 5 + k] = k < m.n ? m.w[k] : 0.f;
+        float *oc = outChain + (size_t)i * 3 * dim, *og = outGauss + (size_t)i * (3 * dim + 1);
+        for (int k = 0; k < dim; k++) {
+            oc[k] = chain.v1[k], oc[dim + k] = chain.v2[k], oc[2 * dim + k] = chain.last_pss[k];
+            og[k] = g.mean[k], og[dim + k] = g.covL_d[k], og[2 * dim + k] = g.invCov_d[k];
+        }
+        og[3 * dim] = g.logDet;
+    }
+    return 0;
+}
 // ComputeGaussian (mala.cpp:7-52) + GaussianLogPdf probe: out = [mean(dim), covL(dim), invCov(dim), logDet, logpdf(offset)]
 void orc_compute_gaussian(int dim, const float *v1, const float *M, float ss, float shk, float sc, const float *offset, float *out) {
     std::vector<Float> a(v1, v1 + dim), mm(M, M + dim), off(offset, offset + dim);

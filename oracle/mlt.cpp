@@ -352,13 +352,14 @@ Float CacheDim::evalPdfCache(const std::vector<Float> &pss_query, const Path &pa
     return ret;
 }
 
-bool CacheDim::query(const std::vector<Float> &pss_, std::vector<Float> &v1_, std::vector<Float> &v2_) const {  // global_cache.h:96-124
+bool CacheDim::query(const std::vector<Float> &pss_, std::vector<Float> &v1_, std::vector<Float> &v2_, Matches *matches) const {  // global_cache.h:96-124
     if (!is_ready) return false;
     const int knn = 5;
     const Float radius = dim * (PSS_QUERY_DIST * PSS_QUERY_DIST);
     int idx[5];
     Float dist[5];
     const int nMatches = tree.RadiusSearch(pss_.data(), radius, knn, idx, dist);
+    if (matches) matches->n = nMatches;
     if (!nMatches) return false;
     double sum_w = 0;
     std::fill(v1_.begin(), v1_.end(), Float(0.0));
@@ -367,6 +368,7 @@ bool CacheDim::query(const std::vector<Float> &pss_, std::vector<Float> &v1_, st
         int index = idx[k];
         Float d = dist[k];
         Float w = inverse(d * d + Float(1e-6));
+        if (matches) matches->idx[k] = index, matches->w[k] = w;
         for (int i = 0; i < dim; i++) {
             v1_[i] += v1[(size_t)index * dim + i] * w;
             v2_[i] += v2[(size_t)index * dim + i] * w;
@@ -734,36 +736,42 @@ void MLT::InitGaussianFor(ChainCtx &c, MarkovState &state, bool isProposal) {
         ComputeGaussianMALA(dim, new_v1, new_v2, chain->ss, sc->options->malaStdDev, chain->M, chain->t, cspContrib.ssScore, state.gaussian);
     } else {
         if (dim >= PSS_MIN_LENGTH && dim <= PSS_MAX_LENGTH && cache.isReady(dim)) {
-            bool reuse = false;
-            if (chain->queried) {
-                Float dist_sqr(0.f);
-                for (int i = 0; i < dim; i++) {
-                    Float diff = chain->pss[i] - chain->last_pss[i];
-                    dist_sqr += diff * diff;
-                }
-                if (dist_sqr < dim * (PSS_REUSE_DIST * PSS_REUSE_DIST)) reuse = true;
-            }
-            auto fromV = [&]() {
-                for (int i = 0; i < dim; i++) chain->M[i] = Clamp(Float(1.0) / Float(Float(1e-3) + std::sqrt(chain->v2[i])), PCD_MIN, PCD_MAX);
-                ComputeGaussianMALA(dim, chain->v1, chain->v2, chain->ss, sc->options->malaStdDev, chain->M, chain->t, cspContrib.ssScore, state.gaussian);
-            };
-            if (reuse) {
-                fromV();
-            } else {
-                c.st->cacheQueries++;
-                if (cache.dims[dim].query(chain->pss, chain->v1, chain->v2)) {
-                    c.st->cacheHits++;
-                    chain->queried = true;
-                    chain->last_pss = chain->pss;
-                    fromV();
-                } else {
-                    IsotropicGaussian(dim, sc->options->malaStdDev, state.gaussian);
-                }
-            }
+            CacheReadyGaussian(cache.dims[dim], *chain, dim, sc->options->malaStdDev, cspContrib.ssScore, state.gaussian, *c.st);
         } else
             IsotropicGaussian(dim, sc->options->malaStdDev, state.gaussian);
     }
     state.gaussianInitialized = true;
+}
+
+CacheBranch CacheReadyGaussian(const CacheDim &cd, Chain &chain, int dim, Float malaStdDev, Float ssScore, Gaussian &gaussian, StepStats &st,
+                               CacheDim::Matches *matches) {
+    bool reuse = false;
+    if (chain.queried) {
+        Float dist_sqr(0.f);
+        for (int i = 0; i < dim; i++) {
+            Float diff = chain.pss[i] - chain.last_pss[i];
+            dist_sqr += diff * diff;
+        }
+        if (dist_sqr < dim * (PSS_REUSE_DIST * PSS_REUSE_DIST)) reuse = true;
+    }
+    auto fromV = [&]() {
+        for (int i = 0; i < dim; i++) chain.M[i] = Clamp(Float(1.0) / Float(Float(1e-3) + std::sqrt(chain.v2[i])), PCD_MIN, PCD_MAX);
+        ComputeGaussianMALA(dim, chain.v1, chain.v2, chain.ss, malaStdDev, chain.M, chain.t, ssScore, gaussian);
+    };
+    if (reuse) {
+        fromV();
+        return CACHE_BRANCH_REUSE;
+    }
+    st.cacheQueries++;
+    if (cd.query(chain.pss, chain.v1, chain.v2, matches)) {
+        st.cacheHits++;
+        chain.queried = true;
+        chain.last_pss = chain.pss;
+        fromV();
+        return CACHE_BRANCH_BLEND;
+    }
+    IsotropicGaussian(dim, malaStdDev, gaussian);
+    return CACHE_BRANCH_ISOTROPIC;
 }
 
 Float MLT::MALAMutate(ChainCtx &c) {  // mutation_mala.h:35-278

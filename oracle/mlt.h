@@ -88,7 +88,13 @@ struct CacheDim {  // global_cache_t<dim>, global_cache.h:33-124 (sampleCache/ev
     bool push(const Float *pss_, const Float *v1_, const Float *v2_, Float weight, const Path &path, const SubpathContrib &spContrib);
     int sampleCache(Float u) const;                                             // global_cache.h:126-137: the row index
     Float evalPdfCache(const std::vector<Float> &pss_query, const Path &path) const;  // global_cache.h:139-164
-    bool query(const std::vector<Float> &pss_, std::vector<Float> &v1_, std::vector<Float> &v2_) const;
+    // matches (optional): what the search returned, in search order, with the blend weight of every row
+    struct Matches {
+        int n = 0;
+        int idx[5] = {-1, -1, -1, -1, -1};
+        Float w[5] = {0, 0, 0, 0, 0};
+    };
+    bool query(const std::vector<Float> &pss_, std::vector<Float> &v1_, std::vector<Float> &v2_, Matches *matches = nullptr) const;
 };
 
 struct GlobalCache {
@@ -113,6 +119,14 @@ struct Chain {  // mutation.h:28-43
     int chainId = 0, t = 0;
     bool queried = false;
 };
+
+struct StepStats;
+// The cache-ready branch of MALASmallStep's Gaussian initialisation (mutation_mala.h:131-164 / :224-257) for a state whose primary sample is in
+// chain.pss: re-use test against last_pss, CacheDim::query, ComputeGaussianMALA from chain.v1 / v2 or the isotropic Gaussian.  Needs no scene:
+// MLT::InitGaussianFor calls it, and so does the probe orc_cache_gaussian (capi.cpp) on caller-given rows and chain states.
+enum CacheBranch { CACHE_BRANCH_ISOTROPIC = 0, CACHE_BRANCH_REUSE = 1, CACHE_BRANCH_BLEND = 2 };
+CacheBranch CacheReadyGaussian(const CacheDim &cd, Chain &chain, int dim, Float malaStdDev, Float ssScore, Gaussian &gaussian, StepStats &st,
+                               CacheDim::Matches *matches = nullptr);
 
 typedef void (*PathFuncDerv)(const Float *, const Float *, const Float *, const Float *, Float *, Float *);
 typedef void (*PathFunc)(const Float *, const Float *, const Float *, const Float *, Float *);

@@ -43,6 +43,7 @@ def load(so):
     L.orc_fastlog.argtypes = [ctypes.c_int, vp, vp]
     L.orc_kd_query.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_float, ctypes.c_int, vp, vp, vp]
     L.orc_compute_gaussian.argtypes = [ctypes.c_int, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp]
+    L.orc_cache_gaussian.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_float, ctypes.c_float, ctypes.c_int] + [vp] * 10
     return L
 
 
