@@ -257,6 +257,49 @@ int lmc_cache_filter_probe(int dim, int npts, const float *pts, int nq, const fl
 int lmc_lean_query_probe(int dim, int npts, const float *pts, const float *v1, const float *v2, float mala_stepsize, float mala_stddev, int grid_m,
                          int chosen_coords, int device_grid, int nq, const float *q, const int *queried, const float *last_pss, const float *ch_v1,
                          const float *ch_v2, const float *ss_score, int *out_int, float *out_w, float *out_chain, float *out_gauss, float *out_generic);
+/* Test probes of the bookkeeping launches the step kernels run on (device/kernels.hip, device/relocate.hip; host/list_probes.cpp): each copies the
+ * caller's arrays to the device, calls the launch function the renderer calls, unchanged, on a stream, waits and copies the results back.  No context;
+ * device 0.  All results are integers or copied words: the references (tests/list_cases.py) are exact.  Return 0, -1 on error.
+ *   lmc_scan_probe              LaunchInclusiveScan: out[i] = in[0] + .. + in[i] (int32; n >= 1 -- the renderer's callers pass 256 or more, n = 0 is not a call)
+ *   lmc_radix_sort_probe        LaunchRadixSort24 on n_max keys of 24 bits of which the first n count (n lives in device memory, 0 <= n <= n_max, n_max >= 1):
+ *                               out_vals[p] = index of the p-th key in stable ascending order, out_keys[p] = that key; both n_max long, the entries from n on
+ *                               hold the sentinel LMC_PROBE_SENTINEL
+ *   lmc_sort_by_technique_probe LaunchSortByTechnique: the first n_list entries of list (chain ids < n_chains) grouped by next_kind[chain] >> 2 into out
+ *                               (n_list entries; the rest of a max_entries-long device array is pre-filled with the sentinel and must stay: checked by the probe).
+ *                               max_entries >= n_list: the capacity the (chunk, key) histogram is sized for (the renderer passes its chain count);
+ *                               0 is legal with an empty list and launches nothing
+ *   lmc_build_lists_probe       LaunchBuildLists over next_kind[N] (sort_plain 0 .. 3, lean_dims as the renderer passes it: bit 2 * (3 + path-length class) = that
+ *                               cache is ready, bit 31 = lean launch without light sub-paths): out_large / out_generic / out_plain N entries each (sentinel beyond
+ *                               the counts), out_counts[3], out_step_kind[N] with want_step_kind (else the launch gets no stepKind array and the pointer may be NULL)
+ *   lmc_bins_compact_probe      LaunchBinsCompact: bin_of[N] (-1: takes no part), count[LMC_PROBE_BINS] = entries of the list per bin, list[n_list] ->
+ *                               out_items[N] (sentinel beyond the total), out_start[LMC_PROBE_BINS]
+ *   lmc_split_list_probe        LaunchSplitList: list[n_list] cut into `parts` (1 .. 4) sub-lists of `stride` entries each -> out_sub[parts * stride] (sentinel where
+ *                               nothing is written), out_sub_count[parts]
+ *   lmc_cache_push_probe        LaunchCachePush: push_dim[N] and push_data[N x 37] (per SLOT: pss[12], v1[12], v2[12], weight; the probe lays them out as the chains' pushData),
+ *                               slot_of[N] chain -> slot or NULL (identity), initial_counts[4] rows already in the dims 6, 8, 10, 12.  Targets of LMC_PROBE_CACHE_ROWS
+ *                               rows per dim, pre-filled with NaN of payload 0x7fc0beef; out_rows[4 x 3 x LMC_PROBE_CACHE_ROWS x 12] = pss | v1 | v2 of every dim
+ *                               (row r, word k of array a of dim slot s at ((s * 3 + a) * ROWS + r) * 12 + k, the words from the dim on untouched),
+ *                               out_weights[4 x ROWS], out_counts[4], out_push_dim[N] = push_dim afterwards
+ *   lmc_reloc_plan_probe        LaunchRelocPlan (count, offsets, assign of LaunchRelocate): step_kind[N] (unsigned char), c[N], l[N] (words 0 and 1 of the
+ *                               contribution), flags[N], placed_key[N]; count[1] = skipped_before going in.  out_count[2], out_members[N], out_sorted[N]
+ *                               (sentinel beyond out_count[0] members ... beyond the members FOUND when the relocation is skipped: the lists are built either way) */
+#define LMC_PROBE_SENTINEL (-0x5a5a5a5b)
+#define LMC_PROBE_BINS 336
+#define LMC_PROBE_CACHE_ROWS 3000
+int lmc_scan_probe(int n, const int *in, int *out);
+int lmc_radix_sort_probe(int n, int n_max, const unsigned *keys, int *out_vals, unsigned *out_keys);
+int lmc_sort_by_technique_probe(int n_chains, const unsigned char *next_kind, int n_list, const int *list, int max_entries, int *out);
+int lmc_build_lists_probe(int N, const unsigned char *next_kind, int sort_plain, unsigned lean_dims, int want_step_kind, int *out_large, int *out_generic,
+                          int *out_plain, int *out_counts, unsigned char *out_step_kind);
+int lmc_bins_compact_probe(int N, const int *bin_of, const int *count, int n_list, const int *list, int grid_blocks, int *out_items, int *out_start);
+int lmc_split_list_probe(int n_list, const int *list, int parts, int stride, int grid_blocks, int *out_sub, int *out_sub_count);
+int lmc_cache_push_probe(int N, const int *push_dim, const float *push_data, const int *slot_of, const int *initial_counts, float *out_rows, float *out_weights,
+                         int *out_counts, int *out_push_dim);
+int lmc_reloc_plan_probe(int N, const unsigned char *step_kind, const int *c, const int *l, const int *flags, const unsigned *placed_key, int without_gaussian_only,
+                         int capacity, int skipped_before, int *out_count, int *out_members, int *out_sorted);
+/* test probe, read-only: where the resident chains live once relocation is on (device/relocate.hip): slot_of[chain] and chain_id[slot], N ints each (either may
+ * be NULL), copied after every stream of the context has drained.  Returns 0, -1 when relocation is off (or no chains are set up), -2 on error. */
+int lmc_chain_slots(lmc_ctx *ctx, int *slot_of, int *chain_id);
 /* ComputeGaussian (mala.cpp:7-52) + GaussianLogPdf (gaussian.cpp:24-36): out n x (3*dim+2) */
 int lmc_gauss_probe(int n, int dim, const float *v1, const float *M, float ss, float shk, const float *sc, const float *offset, float *out);
 /* Parity probes of the H2MC step's own launches (device/h2hess.hip, h2gauss.hip; reference: the evaluate_path_bidir_<c>_<l>_static_derv

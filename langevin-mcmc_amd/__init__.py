@@ -106,6 +106,17 @@ def lib():
             L.lmc_film_read_fixed.argtypes = [vp, vp]
             L.lmc_film_overflow.argtypes = [vp, vp]
             L.lmc_film_splat_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
+        if hasattr(L, "lmc_scan_probe"):  # (an A/B library built from an older tree, LMC_LIB, has no list probes)
+            ci, cu = ctypes.c_int, ctypes.c_uint
+            L.lmc_scan_probe.argtypes = [ci, vp, vp]
+            L.lmc_radix_sort_probe.argtypes = [ci, ci, vp, vp, vp]
+            L.lmc_sort_by_technique_probe.argtypes = [ci, vp, ci, vp, ci, vp]
+            L.lmc_build_lists_probe.argtypes = [ci, vp, ci, cu, ci, vp, vp, vp, vp, vp]
+            L.lmc_bins_compact_probe.argtypes = [ci, vp, vp, ci, vp, ci, vp, vp]
+            L.lmc_split_list_probe.argtypes = [ci, vp, ci, ci, ci, vp, vp]
+            L.lmc_cache_push_probe.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.lmc_reloc_plan_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+            L.lmc_chain_slots.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
 
@@ -317,6 +328,16 @@ class Renderer:
             raise RuntimeError(_err())
         return dict(launches=o[0], chain_steps=o[1], lock_steps=o[2], k=o[3], kernel_ms=ms.value, guard=int(self.get_option("resident_guard")))
 
+    def chain_slots(self):
+        """Test probe: (slot_of[chain], chain_id[slot]) of the resident chains, or None when chain relocation is off"""
+        so, ci = np.full(self.num_chains, -1, np.int32), np.full(self.num_chains, -1, np.int32)
+        r = lib().lmc_chain_slots(self.h, P(so), P(ci))
+        if r == -1:
+            return None
+        if r != 0:
+            raise RuntimeError(_err())
+        return so, ci
+
     def summary(self, which=0):
         n = self.num_chains  # which = 0: current states, 1: init states -- of this rank's chains
         out = np.zeros((n, 32), np.float32)
@@ -480,6 +501,99 @@ def film_splat_probe(width, height, screen_xy, rgb, exact=True):
     if lib().lmc_film_splat_probe(int(width), int(height), len(xy), P(xy), P(c), 1 if exact else 0, P(fx) if exact else None, P(fl), ctypes.byref(ov)) != 0:
         raise RuntimeError("lmc_film_splat_probe failed: " + _err())
     return fx, fl, int(ov.value)
+
+
+# ---- test probes of the bookkeeping launches (include/lmc_abi.h; references in tests/list_cases.py).  Integer arrays in, integer arrays out.
+PROBE_SENTINEL = -0x5A5A5A5B  # what a probe's output holds where the launch wrote nothing
+PROBE_BINS = 336
+PROBE_CACHE_ROWS = 3000
+PROBE_UNTOUCHED_BITS = 0x7FC0BEEF  # ... and a float output: a NaN with this bit pattern
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _probe(name, r):
+    if r != 0:
+        raise RuntimeError("%s failed: %s" % (name, _err()))
+
+
+def scan_probe(values):
+    """LaunchInclusiveScan on int32 values (at least one): the inclusive prefix sums, int32"""
+    v = _i32(values)
+    out = np.full(len(v), PROBE_SENTINEL, np.int32)
+    _probe("lmc_scan_probe", lib().lmc_scan_probe(len(v), P(v), P(out)))
+    return out
+
+
+def radix_sort_probe(keys, n=None):
+    """LaunchRadixSort24 on the first n of the len(keys) 24-bit keys (n lives in device memory): (vals, sorted keys), both len(keys) long"""
+    k = np.ascontiguousarray(keys, np.uint32)
+    n = len(k) if n is None else int(n)
+    vals, out = np.zeros(len(k), np.int32), np.zeros(len(k), np.uint32)
+    _probe("lmc_radix_sort_probe", lib().lmc_radix_sort_probe(n, len(k), P(k), P(vals), P(out)))
+    return vals, out
+
+
+def sort_by_technique_probe(next_kind, entries, max_entries):
+    """LaunchSortByTechnique: the list's entries grouped by next_kind[chain] >> 2; the probe itself checks that nothing beyond the count is written"""
+    nk, e = np.ascontiguousarray(next_kind, np.uint8), _i32(entries)
+    out = np.full(len(e), PROBE_SENTINEL, np.int32)
+    _probe("lmc_sort_by_technique_probe", lib().lmc_sort_by_technique_probe(len(nk), P(nk), len(e), P(e), int(max_entries), P(out)))
+    return out
+
+
+def build_lists_probe(next_kind, sort_plain, lean_dims=0, want_step_kind=True):
+    """LaunchBuildLists: dict(large, generic, plain: N entries each, the sentinel beyond the count; counts[3]; step_kind[N] or None)"""
+    nk = np.ascontiguousarray(next_kind, np.uint8)
+    n = len(nk)
+    o = dict(large=np.zeros(n, np.int32), generic=np.zeros(n, np.int32), plain=np.zeros(n, np.int32), counts=np.zeros(3, np.int32),
+             step_kind=np.zeros(n, np.uint8) if want_step_kind else None)
+    _probe("lmc_build_lists_probe", lib().lmc_build_lists_probe(n, P(nk), int(sort_plain), int(lean_dims) & 0xFFFFFFFF, 1 if want_step_kind else 0, P(o["large"]),
+                                                              P(o["generic"]), P(o["plain"]), P(o["counts"]), P(o["step_kind"]) if want_step_kind else None))
+    return o
+
+
+def bins_compact_probe(bin_of, count, entries, grid_blocks):
+    """LaunchBinsCompact: (items[N], start[PROBE_BINS])"""
+    b, c, e = _i32(bin_of), _i32(count), _i32(entries)
+    if len(c) != PROBE_BINS:
+        raise ValueError("bins_compact_probe: count has %d entries, not %d" % (len(c), PROBE_BINS))
+    items, start = np.zeros(len(b), np.int32), np.zeros(PROBE_BINS, np.int32)
+    _probe("lmc_bins_compact_probe", lib().lmc_bins_compact_probe(len(b), P(b), P(c), len(e), P(e), int(grid_blocks), P(items), P(start)))
+    return items, start
+
+
+def split_list_probe(entries, parts, stride, grid_blocks):
+    """LaunchSplitList: (sub[parts, stride], sub_count[parts])"""
+    e = _i32(entries)
+    sub, cnt = np.zeros((parts, stride), np.int32), np.zeros(parts, np.int32)
+    _probe("lmc_split_list_probe", lib().lmc_split_list_probe(len(e), P(e), int(parts), int(stride), int(grid_blocks), P(sub), P(cnt)))
+    return sub, cnt
+
+
+def cache_push_probe(push_dim, push_data, slot_of, initial_counts):
+    """LaunchCachePush: push_dim[N] and push_data[N, 37] (pss 12 | v1 12 | v2 12 | weight) by slot, slot_of[N] or None ->
+    (rows float32 [4 dims, 3 arrays, PROBE_CACHE_ROWS, 12], weights [4, PROBE_CACHE_ROWS], counts[4], push_dim afterwards)"""
+    d, x, c0 = _i32(push_dim), np.ascontiguousarray(push_data, np.float32), _i32(initial_counts)
+    if x.shape != (len(d), 37) or len(c0) != 4:
+        raise ValueError("cache_push_probe: push_data must be N x 37, initial_counts 4 long")
+    so = None if slot_of is None else _i32(slot_of)
+    rows, w = np.zeros((4, 3, PROBE_CACHE_ROWS, 12), np.float32), np.zeros((4, PROBE_CACHE_ROWS), np.float32)
+    counts, after = np.zeros(4, np.int32), np.zeros(len(d), np.int32)
+    _probe("lmc_cache_push_probe", lib().lmc_cache_push_probe(len(d), P(d), P(x), None if so is None else P(so), P(c0), P(rows), P(w), P(counts), P(after)))
+    return rows, w, counts, after
+
+
+def reloc_plan_probe(step_kind, c, l, flags, placed_key, without_gaussian_only, capacity, skipped_before):
+    """LaunchRelocPlan: (count[2], members[N], sorted[N])"""
+    sk, c, l, f, pk = np.ascontiguousarray(step_kind, np.uint8), _i32(c), _i32(l), _i32(flags), np.ascontiguousarray(placed_key, np.uint32)
+    n = len(sk)
+    count, members, srt = np.zeros(2, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _probe("lmc_reloc_plan_probe", lib().lmc_reloc_plan_probe(n, P(sk), P(c), P(l), P(f), P(pk), 1 if without_gaussian_only else 0, int(capacity), int(skipped_before),
+                                                            P(count), P(members), P(srt)))
+    return count, members, srt
 
 
 def comm_unique_id():

@@ -139,6 +139,8 @@ size_t RelocRecordWords(int maxDepth);
 void LaunchRelocIota(int n, int *v, hipStream_t s);
 // withoutGaussianOnly (H2MC renders): chains that hold a stored Gaussian stay where they are (the pipeline's Gaussian buffers are per slot)
 void LaunchRelocate(const lmcd::ChainArrays &A, int maxDepth, const RelocBuffers &B, bool withoutGaussianOnly, hipStream_t s);
+// its first half on its own (the three launches that fill B.members / B.sorted / B.count; LaunchRelocate = this + the move): what lmc_reloc_plan_probe runs
+void LaunchRelocPlan(const lmcd::ChainArrays &A, int maxDepth, const RelocBuffers &B, bool withoutGaussianOnly, hipStream_t s);
 void LaunchRelocFineKey(const lmcd::ChainArrays &A, const int *leafPosOfTri, int numTris, int mode, unsigned long long *keys, const lmcd::TriData *tris, const lmcd::DMaterial *materials, hipStream_t s);
 void LaunchRelocMove(const lmcd::ChainArrays &A, int maxDepth, const RelocBuffers &B, hipStream_t s, int keyMode = 0);
 // the periodic full re-sort by (technique, screen Morton code): work buffers of the device radix sort
@@ -149,6 +151,9 @@ struct RelocSortBuffers {
     int *scanSums;      // 256 x RelocSortBlocks(N) / 2048 + 2
 };
 size_t RelocSortBlocks(int N);
+// the stable 24-bit sort itself: keys in W.keys[0][0 .. *nPtr) (the count lives on the device, at most nMax; W sized for nMax) -> out[p] = index of the p-th key,
+// the sorted keys in W.keys[1]; entries from *nPtr on are not written
+void LaunchRadixSort24(const RelocSortBuffers &W, const int *nPtr, int nMax, int *out, hipStream_t s);
 void LaunchRelocFullSort(const lmcd::ChainArrays &A, int maxDepth, const RelocBuffers &B, const RelocSortBuffers &W, hipStream_t s);
 void LaunchRelocateFine(const lmcd::ChainArrays &A, int maxDepth, const RelocBuffers &B, const RelocSortBuffers &W, bool withoutGaussianOnly, hipStream_t s);
 // dilated grid of one cache dim on the device (DCacheDim::gridStart / gridRows); buffer sizes in kernels.hip

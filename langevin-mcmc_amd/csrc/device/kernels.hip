@@ -1043,6 +1043,7 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const unsigned char *nextK
 // blockHist: 64 ints per SORT_CHUNK entries of the longest possible list (maxEntries)
 void LaunchSortByTechnique(const unsigned char *nextKind, const int *in, int *out, const int *count, int *blockHist, int maxEntries, hipStream_t s) {
     const int nBlocks = (maxEntries + SORT_CHUNK - 1) / SORT_CHUNK;
+    if (nBlocks <= 0) return;  // a list without room for an entry: nothing to sort, and a launch of zero blocks is refused (invalid configuration)
     hipLaunchKernelGGL(k_sort_hist, dim3(nBlocks), dim3(256), 0, s, nextKind, in, count, blockHist);
     hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(64), 0, s, count, blockHist);
     hipLaunchKernelGGL(k_sort_scatter, dim3(nBlocks), dim3(256), 0, s, nextKind, in, out, count, blockHist);

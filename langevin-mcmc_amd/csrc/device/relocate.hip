@@ -704,7 +704,7 @@ void LaunchRelocMove(const ChainArrays &A, int maxDepth, const RelocBuffers &B, 
 size_t RelocSortBlocks(int N) { return (size_t)(N + RS_TILE - 1) / RS_TILE; }
 // every chain re-placed by (technique, screen Morton code); B.capacity must be N (the caller checks).  W: keys[2][N], vals[2][N], hist[256 x RelocSortBlocks(N)], scan tile sums
 // the three stable 8-bit passes over (key, value) pairs: keys W.keys[0] -> [1] -> [0] -> [1], values iota -> W.vals[0] -> W.vals[1] -> out; *nPtr pairs (at most nMax)
-static void LaunchRadixSort24(const RelocSortBuffers &W, const int *nPtr, int nMax, int *out, hipStream_t s) {
+void LaunchRadixSort24(const RelocSortBuffers &W, const int *nPtr, int nMax, int *out, hipStream_t s) {
     const int nBlocks = (int)RelocSortBlocks(nMax);
     const unsigned *kin[3] = {W.keys[0], W.keys[1], W.keys[0]};
     unsigned *kout[3] = {W.keys[1], W.keys[0], W.keys[1]};
@@ -737,13 +737,19 @@ void LaunchRelocateFine(const ChainArrays &A, int maxDepth, const RelocBuffers &
     LaunchMoveKernels(A, R, B, -1, moveBlocks, s);
 }
 
-void LaunchRelocate(const ChainArrays &A, int maxDepth, const RelocBuffers &B, bool withoutGaussianOnly, hipStream_t s) {
-    const RecordLayout R = MakeRecordLayout(maxDepth);
+// who moves, and where (count, offsets, assign): B.members / B.sorted / B.count of one relocation; reads N, stepKind, curContrib words 0 and 1 and flags of A
+void LaunchRelocPlan(const ChainArrays &A, int maxDepth, const RelocBuffers &B, bool withoutGaussianOnly, hipStream_t s) {
     const int N = A.N, nTiles = (N + RELOC_TILE - 1) / RELOC_TILE;
     const int tiles = (LMC_RELOC_TILES && maxDepth <= 6) ? 8 : 0;
     hipLaunchKernelGGL(k_reloc_count, dim3(nTiles), dim3(64), 0, s, A, B.placedKey, B.tileCount, B.tileHist, withoutGaussianOnly, tiles);
     hipLaunchKernelGGL(k_reloc_offsets, dim3(1), dim3(64), 0, s, nTiles, B.tileCount, B.tileHist, B.count, B.capacity);
     hipLaunchKernelGGL(k_reloc_assign, dim3(nTiles), dim3(64), 0, s, A, B.placedKey, B.tileCount, B.tileHist, B.members, B.sorted, withoutGaussianOnly, tiles);
+}
+void LaunchRelocate(const ChainArrays &A, int maxDepth, const RelocBuffers &B, bool withoutGaussianOnly, hipStream_t s) {
+    const RecordLayout R = MakeRecordLayout(maxDepth);
+    const int N = A.N;
+    const int tiles = (LMC_RELOC_TILES && maxDepth <= 6) ? 8 : 0;
+    LaunchRelocPlan(A, maxDepth, B, withoutGaussianOnly, s);
     const int moveBlocks = std::min((N + 63) / 64, 4096);
     LaunchMoveKernels(A, R, B, tiles, moveBlocks, s);
 }

@@ -28,6 +28,7 @@
 #include "../device/dh2coop.h"
 #include "../device/dh2mc.h"
 #include "accel.h"
+#include "last_error.h"
 #include "scene.h"
 #include "shardplan.h"
 
@@ -524,6 +525,8 @@ static void UploadCacheStruct(lmc_ctx *c, hipStream_t after = nullptr) {
 }
 
 // ------------------------------------------------------------------------------------------------ ABI
+void LmcSetLastError(const std::string &what) { g_err = what; }  // last_error.h
+
 extern "C" {
 
 const char *lmc_last_error(void) { return g_err.c_str(); }
@@ -2650,6 +2653,18 @@ long long lmc_relocation_skipped(lmc_ctx *c) {
     if (!c->relocate || c->N <= 0) return -1;
     HIP_CHECK(hipStreamSynchronize(c->stream));
     return c->relocations ? c->relocCount.Download()[1] : 0;
+    LMC_CATCH(-2)
+}
+
+// test probe: where the chains live.  slot_of[chain] and chain_id[slot] as they stand (N ints each, either may be NULL); -1 when relocation is off
+int lmc_chain_slots(lmc_ctx *c, int *slot_of, int *chain_id) {
+    LMC_TRY
+    if (!c->relocate || c->N <= 0) return -1;
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipDeviceSynchronize());  // the relocation runs on the large-step stream: every stream of the context, not just the main one
+    if (slot_of) HIP_CHECK(hipMemcpy(slot_of, c->slotOf.p, (size_t)c->N * sizeof(int), hipMemcpyDeviceToHost));
+    if (chain_id) HIP_CHECK(hipMemcpy(chain_id, c->chainId.p, (size_t)c->N * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
     LMC_CATCH(-2)
 }
 
