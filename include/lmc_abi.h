@@ -148,6 +148,56 @@ int lmc_mc_render(lmc_ctx *ctx, int spp, long long stream_begin, long long strea
 int lmc_mc_read(lmc_ctx *ctx, float *rgb);
 /* out2[0] = paths traced, out2[1] = contributions splatted, by the last lmc_mc_render */
 int lmc_mc_stats(lmc_ctx *ctx, long long *out2);
+/* A render or accumulate call of either film mode runs as launches of at most lmc_set_option "mc_launch_streams" stream ids each (default 262144: a
+ * 1024 x 768 render at 64 spp, 196608 ids, is one launch) on the context's stream; a cut between two launches falls on a multiple of nTiles wherever
+ * one lies inside the launch it ends, and the launches' scratch is sized for one of them.  lmc_get_option "mc_launches" reports the launches of the
+ * last call.  The film does not depend on the cuts (float mode: up to the order of the float adds, as between any two runs).
+ *
+ * Exact mc film (INTEGRATION.md "Exact mc film"): lmc_set_option "mc_film_exact" = 1 (default 0; a name of its own, "film_exact" and LMC_FILM_EXACT
+ * keep governing the MLT film alone) takes effect at the next lmc_mc_render and makes the MC film W*H*3 signed 64-bit fixed-point words holding the
+ * integer sum of the UNWEIGHTED contributions, so that the film is a pure function of the set of stream ids it holds: bit-equal however the ids are
+ * cut into calls, launches, members or files, and from run to run.
+ *   conversion   q = llrint((double)v * 4294967296.0) per component of a contribution that passed the luminance and finite tests of float mode
+ *   deviations   (1) summed unweighted and divided ONCE, at read time, in double (float mode divides every contribution in float, then sums);
+ *                (2) a contribution with a component |v| >= 2^30 is dropped WHOLE and counted by lmc_mc_overflow; lmc_mc_stats still counts it
+ *   coverage     the film knows the stream ids it holds as disjoint, merged, ascending ranges; a range that overlaps them is refused
+ *   lmc_mc_render       clears words, overflow, counters and coverage, then adds [stream_begin, stream_end) like lmc_mc_accumulate
+ *   lmc_mc_accumulate   adds the ids [stream_begin, stream_end) of [0, nTiles * spp) (-1: to the end) WITHOUT clearing; spp becomes the read divisor.
+ *                       Exact mode only (-1 in float mode).  An overlapping range, or a film that holds ids beyond nTiles * spp, returns -1 and
+ *                       leaves film and coverage as they were.  On a context that holds no exact film yet it starts from an empty one.
+ *   lmc_mc_coverage     returns the number of ranges held and writes at most cap [begin, end) pairs (0 in float mode)
+ *   lmc_mc_read         converts on the device, float((double)q * 2^-32 / (double)spp), spp the divisor of the latest render / accumulate / load
+ *   lmc_mc_read_fixed   the W*H*3 raw words; -1 in float mode
+ *   lmc_mc_overflow     *n = contributions dropped by the range rule since the film was last cleared (0 in float mode)
+ *   lmc_mc_stats        cumulative since the film was last cleared
+ * lmc_group_mc_render (either mode): [stream_begin, stream_end) split at begin + (end - begin) * k / n, member k renders shard k concurrently with the
+ * others (one host thread each), then member 0's film becomes the sum over the members, added in ascending member order on member 0's device (int64
+ * in exact mode; float in float mode, the order a host loop over the members adds in).  Member 0's stats, overflow and coverage are the whole's, the
+ * other members' MC films and counters are left cleared.  The members are distinct contexts of one scene (a device may carry several); members that
+ * differ in "mc_film_exact" are refused before anything is rendered.  lmc_group_mc_accumulate (exact mode only): the same, except that member 0 adds
+ * its shard to the film it holds (after lmc_mc_load, say), so it ends with what it held plus the whole range; a range that overlaps member 0's
+ * coverage is refused before anything is rendered.
+ * State file (exact mode only): lmc_mc_save writes path.tmp and renames it; little-endian: magic "LMCMCFX\n", uint32 version (1), uint32 R, uint64 scene hash
+ * (content of the XML and the files it pulls in), int32 force_diffuse, width, height, mindepth, maxdepth, seedoffset, bidirectional, 0, int64 nTiles,
+ * divisor spp, paths, contributions, overflow, R x int64 [begin, end) coverage ranges, W*H*3 int64 words.  lmc_mc_load ("mc_film_exact" = 1 on the
+ * context) compares scene hash .. nTiles field by field and returns -1 naming the first that differs -- or a wrong magic, a wrong version, a short
+ * file -- leaving the context as it was; after it lmc_mc_accumulate continues the render.  lmc_mc_file_info: host only, the header as JSON
+ * (lmc_checkpoint_info's convention).
+ * Not covered: the RCCL rank path (lmc_film_allreduce sums the MLT film only), lmc_path_trace, lmc_bidir_mc and the direct film stay float. */
+int lmc_mc_accumulate(lmc_ctx *ctx, int spp, long long stream_begin, long long stream_end);
+int lmc_mc_coverage(lmc_ctx *ctx, long long *ranges, int cap);
+int lmc_mc_read_fixed(lmc_ctx *ctx, long long *words);
+int lmc_mc_overflow(lmc_ctx *ctx, long long *n);
+int lmc_group_mc_render(lmc_ctx **ctxs, int n, int spp, long long stream_begin, long long stream_end);
+int lmc_group_mc_accumulate(lmc_ctx **ctxs, int n, int spp, long long stream_begin, long long stream_end);
+int lmc_mc_save(lmc_ctx *ctx, const char *path);
+int lmc_mc_load(lmc_ctx *ctx, const char *path);
+long long lmc_mc_file_info(const char *path, char *json, long long cap);
+/* test hooks of the host-side bookkeeping (host/mcfilm.cpp), host only.  coverage_probe: the n_adds ranges adds[2 i], adds[2 i + 1] are added in turn to an
+ * empty coverage, accepted[i] = 1 / 0; cov / comp receive the ranges then held / what [0, total) lacks (at most their cap pairs; *n_cov / *n_comp the full
+ * numbers).  chunks_probe: the launches a call over [begin, end) is cut into; returns their number, writes at most cap pairs. */
+int lmc_mc_coverage_probe(const long long *adds, int n_adds, long long total, int *accepted, long long *cov, int cov_cap, int *n_cov, long long *comp, int comp_cap, int *n_comp);
+int lmc_mc_chunks_probe(long long begin, long long end, long long n_tiles, long long launch_streams, long long *out, int cap);
 /* out[0..7] = steps, largeSteps, accepted, gradCalls, cacheQueries, cacheHits, resets, cacheReadyMask; *weight_sum =
  * sum over steps of the splatted weight (film luminance == normalization * weight_sum) */
 int lmc_stats(lmc_ctx *ctx, long long *out8, double *weight_sum);
@@ -355,7 +405,8 @@ long long lmc_checkpoint_info(const char *path, char *json, long long cap);
  *                         (the in-process group is checked; rank processes are the caller's to configure alike)
  *   checkpoints           store the int64 film (format version 2, "film_format":"fixed64" in lmc_checkpoint_info); float-mode files are version 1,
  *                         byte for byte as before; a file loads only into a context of its own mode
- * The direct-lighting and mc-integrator films (lmc_direct_read, lmc_mc_read) are float in either mode. */
+ * The direct-lighting and mc-integrator films (lmc_direct_read, lmc_mc_read) are float in either mode; the mc film has an exact mode of its own,
+ * "mc_film_exact" (above). */
 int lmc_film_read_fixed(lmc_ctx *ctx, long long *out);
 int lmc_film_overflow(lmc_ctx *ctx, long long *n);
 /* test probe: n splats (screen_xy n x 2 in [0,1)^2, rgb n x 3) through the device's splat routine into a fresh W x H film, one launch of n lanes in

@@ -78,6 +78,19 @@ def lib():
             L.lmc_mc_render.argtypes = [vp, ctypes.c_int, c_ll, c_ll]
             L.lmc_mc_read.argtypes = [vp, vp]
             L.lmc_mc_stats.argtypes = [vp, vp]
+        if hasattr(L, "lmc_mc_accumulate"):  # (an A/B library built from an older tree, LMC_LIB, has no exact mc film)
+            L.lmc_mc_accumulate.argtypes = [vp, ctypes.c_int, c_ll, c_ll]
+            L.lmc_mc_coverage.argtypes = [vp, vp, ctypes.c_int]
+            L.lmc_mc_read_fixed.argtypes = [vp, vp]
+            L.lmc_mc_overflow.argtypes = [vp, vp]
+            L.lmc_group_mc_render.argtypes = [vp, ctypes.c_int, ctypes.c_int, c_ll, c_ll]
+            L.lmc_group_mc_accumulate.argtypes = [vp, ctypes.c_int, ctypes.c_int, c_ll, c_ll]
+            L.lmc_mc_save.argtypes = [vp, ctypes.c_char_p]
+            L.lmc_mc_load.argtypes = [vp, ctypes.c_char_p]
+            L.lmc_mc_file_info.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_ll]
+            L.lmc_mc_file_info.restype = c_ll
+            L.lmc_mc_coverage_probe.argtypes = [vp, ctypes.c_int, c_ll, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp]
+            L.lmc_mc_chunks_probe.argtypes = [c_ll, c_ll, c_ll, c_ll, vp, ctypes.c_int]
         L.lmc_stream_probe.argtypes = [c_ll, ctypes.c_int]
         L.lmc_grad_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
         L.lmc_trace.argtypes = [vp, ctypes.c_int, vp, vp, vp]
@@ -283,7 +296,9 @@ class Renderer:
     def mc_render(self, spp, streams=None):
         """The scene's "mc" integrator (PathTrace): spp samples per pixel, bidirectional or not as the scene says (set_option "bidirectional"
         overrides it); radiance image [H, W, 3], already weighted by 1 / spp.  streams=(begin, end): only those stream ids of
-        [0, nTiles * spp) (end -1: to the last one); the films of disjoint ranges sum to the film of their union."""
+        [0, nTiles * spp) (end -1: to the last one); the films of disjoint ranges sum to the film of their union.  After
+        set_option("mc_film_exact", 1) the film is the fixed-point sum of the unweighted contributions (mc_film_fixed) and what is returned is
+        that sum divided by spp; mc_accumulate then adds further ranges."""
         begin, end = (0, -1) if streams is None else (int(streams[0]), int(streams[1]))
         if lib().lmc_mc_render(self.h, int(spp), begin, end) != 0:
             raise RuntimeError(_err())
@@ -293,11 +308,61 @@ class Renderer:
         return out
 
     def mc_stats(self):
-        """(paths traced, contributions splatted) of the last mc_render"""
+        """(paths traced, contributions splatted) of the last mc_render; with the exact mc film: since the film was last cleared"""
         o = (c_ll * 2)()
         if lib().lmc_mc_stats(self.h, o) != 0:
             raise RuntimeError(_err())
         return int(o[0]), int(o[1])
+
+    # ---- the exact mc film (set_option("mc_film_exact", 1) before mc_render; include/lmc_abi.h "Exact mc film")
+    def mc_film(self):
+        """the mc film as mc_render returned it, read again (exact mode: the words divided by the latest call's spp)"""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        if lib().lmc_mc_read(self.h, P(out)) != 0:
+            raise RuntimeError(_err())
+        return out
+
+    def mc_accumulate(self, spp, streams=None):
+        """Adds the stream ids streams=(begin, end) of [0, nTiles * spp) to the exact mc film without clearing it; spp becomes the read divisor.
+        A range that overlaps what the film holds raises and leaves the film as it was.  Returns the film like mc_render."""
+        begin, end = (0, -1) if streams is None else (int(streams[0]), int(streams[1]))
+        if lib().lmc_mc_accumulate(self.h, int(spp), begin, end) != 0:
+            raise RuntimeError("lmc_mc_accumulate failed: " + _err())
+        return self.mc_film()
+
+    def mc_film_fixed(self):
+        """the exact mc film's raw words, int64 [H, W, 3] (unit 2^-32, unweighted); raises in float mode"""
+        f = np.zeros((self.height, self.width, 3), np.int64)
+        if lib().lmc_mc_read_fixed(self.h, P(f)) != 0:
+            raise RuntimeError("lmc_mc_read_fixed failed: " + _err())
+        return f
+
+    def mc_overflow(self):
+        """contributions the exact mc film dropped by its range rule (a component |v| >= 2^30) since it was last cleared; 0 in float mode"""
+        n = c_ll()
+        if lib().lmc_mc_overflow(self.h, ctypes.byref(n)) != 0:
+            raise RuntimeError(_err())
+        return int(n.value)
+
+    def mc_coverage(self):
+        """the stream ids the exact mc film holds: a list of disjoint, merged, ascending (begin, end) pairs"""
+        n = lib().lmc_mc_coverage(self.h, None, 0)
+        if n < 0:
+            raise RuntimeError(_err())
+        o = (c_ll * (2 * max(n, 1)))()
+        lib().lmc_mc_coverage(self.h, o, n)
+        return [(int(o[2 * k]), int(o[2 * k + 1])) for k in range(n)]
+
+    def mc_save(self, path):
+        """the exact mc film with its divisor, counters and coverage as one file (written to path + ".tmp", then renamed)"""
+        if lib().lmc_mc_save(self.h, os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_mc_save failed: " + _err())
+
+    def mc_load(self, path):
+        """Replaces the exact mc film by a file's (set_option("mc_film_exact", 1) first); a file of another scene, film size, depth range, seed offset or
+        generator raises naming the field and leaves the context as it was.  mc_accumulate then continues the render."""
+        if lib().lmc_mc_load(self.h, os.fsencode(path)) != 0:
+            raise RuntimeError("lmc_mc_load failed: " + _err())
 
     def stats(self):
         s = (c_ll * 8)()
@@ -462,6 +527,22 @@ class Group:
             raise RuntimeError(_err())
         return dict(devices=o[0], peer_pairs=o[1], peer_pairs_enabled=o[2], host_threads=o[3])
 
+    def mc_render(self, spp, streams=None):
+        """The mc integrator sharded over the members (lmc_group_mc_render): the stream range split into len(members) contiguous shards rendered
+        concurrently, member 0's mc film left as their sum in member order (its mc_stats / mc_overflow / mc_coverage are the whole's), the other
+        members' mc films cleared.  Members that differ in "mc_film_exact" are refused before anything is rendered.  Returns member 0's film."""
+        begin, end = (0, -1) if streams is None else (int(streams[0]), int(streams[1]))
+        if lib().lmc_group_mc_render(self._arr, len(self.rens), int(spp), begin, end) != 0:
+            raise RuntimeError("lmc_group_mc_render failed: " + _err())
+        return self.rens[0].mc_film()
+
+    def mc_accumulate(self, spp, streams=None):
+        """... the same range added to the exact film member 0 already holds (lmc_group_mc_accumulate)"""
+        begin, end = (0, -1) if streams is None else (int(streams[0]), int(streams[1]))
+        if lib().lmc_group_mc_accumulate(self._arr, len(self.rens), int(spp), begin, end) != 0:
+            raise RuntimeError("lmc_group_mc_accumulate failed: " + _err())
+        return self.rens[0].mc_film()
+
     def film_reduce(self):
         """Every member's device film becomes the sum over the members (peer copies: the in-process lmc_film_allreduce); returns its wall time in ms."""
         L = lib()
@@ -486,6 +567,53 @@ def checkpoint_info(path):
     if n < 0:
         raise RuntimeError("lmc_checkpoint_info failed: " + _err())
     return json.loads(buf.value.decode())
+
+
+def mc_file_info(path):
+    """The header of an mc film state file (Renderer.mc_save) as a dict (host only): fingerprint fields, n_tiles, spp (the divisor), paths, contributions,
+    overflow, coverage (a list of [begin, end]), film_words, words_offset, total_bytes."""
+    import json
+
+    buf = ctypes.create_string_buffer(1 << 16)
+    n = lib().lmc_mc_file_info(os.fsencode(path), buf, len(buf))
+    if n < 0:
+        raise RuntimeError("lmc_mc_file_info failed: " + _err())
+    return json.loads(buf.value.decode())
+
+
+def mc_file_words(path):
+    """The film words of an mc film state file, int64 [H, W, 3], read here from the file's bytes (little-endian; layout in include/lmc_abi.h): 96 fixed
+    bytes with the number of coverage ranges R at byte 12 and width, height at bytes 28 and 32, then R x 16 bytes of ranges, then the words."""
+    raw = open(path, "rb").read()
+    if len(raw) < 96 or raw[:8] != b"LMCMCFX\n":
+        raise RuntimeError("mc_file_words: %s is not an mc film state file" % path)
+    n_ranges = int(np.frombuffer(raw, "<u4", 1, 12)[0])
+    width, height = (int(v) for v in np.frombuffer(raw, "<i4", 2, 28))
+    at, n = 96 + 16 * n_ranges, width * height * 3
+    if len(raw) != at + 8 * n:
+        raise RuntimeError("mc_file_words: %s has %d bytes, its header asks for %d" % (path, len(raw), at + 8 * n))
+    return np.frombuffer(raw, "<i8", n, at).astype(np.int64).reshape(height, width, 3)
+
+
+def mc_coverage_probe(adds, total):
+    """Test probe of the coverage arithmetic (host only): the (begin, end) ranges added in turn to an empty coverage ->
+    (accepted flags, ranges held, complement within [0, total))"""
+    a = np.ascontiguousarray(adds, np.int64).reshape(-1, 2)
+    cap = len(a) + 2
+    acc = np.zeros(max(len(a), 1), np.int32)
+    cov, comp = np.zeros((cap, 2), np.int64), np.zeros((cap, 2), np.int64)
+    nc, nm = ctypes.c_int(), ctypes.c_int()
+    if lib().lmc_mc_coverage_probe(P(a), len(a), int(total), P(acc), P(cov), cap, ctypes.byref(nc), P(comp), cap, ctypes.byref(nm)) != 0:
+        raise RuntimeError("lmc_mc_coverage_probe failed")
+    return ([bool(v) for v in acc[: len(a)]], [tuple(int(v) for v in r) for r in cov[: nc.value]], [tuple(int(v) for v in r) for r in comp[: nm.value]])
+
+
+def mc_chunks_probe(begin, end, n_tiles, launch_streams):
+    """Test probe (host only): the launches a render call over [begin, end) is cut into, as (begin, end) pairs"""
+    n = lib().lmc_mc_chunks_probe(int(begin), int(end), int(n_tiles), int(launch_streams), None, 0)
+    o = np.zeros((max(n, 1), 2), np.int64)
+    lib().lmc_mc_chunks_probe(int(begin), int(end), int(n_tiles), int(launch_streams), P(o), n)
+    return [tuple(int(v) for v in r) for r in o[:n]]
 
 
 def film_splat_probe(width, height, screen_xy, rgb, exact=True):

@@ -60,9 +60,12 @@ void LaunchDirect(const lmcd::DScene &S, const lmcd::Film &film, int directSpp, 
                   hipStream_t s);
 void LaunchBidirMC(const lmcd::DScene &S, const lmcd::Film &film, int nThreads, int samplesPerThread, uint32_t *tabScratch, float *contribScratch, hipStream_t s);
 // the mc integrator (mc.hip): stream ids [streamBegin, streamEnd) of nTiles * spp; tabScratch: 64 words per thread (MCThreads), counters: 2 x u64
+// film: float (contributions weighted by 1 / spp) or, with FILM_EXACT in its H (FilmFx), W*H*3 + 1 fixed-point words of unweighted contributions, the last
+// the overflow counter; the launch adds to the film and to the counters, it clears neither
 void LaunchMC(const lmcd::DScene &S, const lmcd::Film &film, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin, long long streamEnd,
               uint32_t *tabScratch, unsigned long long *counters, hipStream_t s);
 long long MCThreads(const lmcd::DScene &S, long long streamBegin, long long streamEnd);
+void LaunchMCFixedToFloat(const long long *fx, float *rgb, size_t n, int spp, hipStream_t s);  // rgb[i] = float(double(fx[i]) * 2^-32 / double(spp))
 void LaunchSetupChains(const lmcd::ChainArrays &A, int chainBegin, long long perChain, long long chainsNeedExtra, hipStream_t s);
 void LaunchFirstKind(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::StepParams &P, hipStream_t s);
 // one of the three step launches (device/step_*.hip): chains of `list` (count read on the device) run one mutation and

@@ -11,6 +11,12 @@
 // pixel at the same time.  A sample's camera-side contributions all land in its own pixel; they are summed in the lane and the lanes of a
 // wave that share a pixel add once (wave reduction) instead of 64 times to the same three floats (MI355X_MICROARCH.md: many adders on one
 // row run ~14x slower).  Light-tracing contributions (ConnectToCamera) land anywhere and are added on the spot.
+//
+// Films.  The sink is a type per film type (dchain.h Film / FilmFixed; LaunchMC picks through DispatchFilm), so the float kernels hold no trace
+// of the exact film.  Exact mode ("mc_film_exact"): the film is the integer sum of the UNWEIGHTED contributions, q = llrint((double)v * 2^32)
+// per component; a contribution with a component |v| >= 2^30 is dropped whole and counted in the film's overflow word (after the contribution
+// counter, which therefore stays the float mode's).  Nothing is divided by spp on the device; lmc_mc_read does that once (k_mc_fixed_to_float).
+// Either kernel only ever adds to the film: clearing it, or not, is the host's business (lmc_mc_render / lmc_mc_accumulate).
 #include "kernels.h"
 #include "ddirect.h"
 
@@ -21,7 +27,10 @@ namespace {
 constexpr float kMcMinLuminance = 1e-10f;  // pathtrace.cpp:60
 
 // where one sample's contributions go: the camera-side ones into the lane's own-pixel sum, the rest straight to the film
-struct McSink {
+template <class FILM>
+struct McSink;
+template <>
+struct McSink<Film> {
     Film film;
     float spp;  // contrib / spp: a division, as Eigen's vector / scalar in the reference
     V3 acc;
@@ -48,6 +57,37 @@ struct McSink {
     LMC_D void Push(const Contrib &c) { Add(c.camDepth != 1, c.screenPos, c.contrib); }  // camDepth 1: ConnectToCamera (light tracing)
     LMC_D void operator()(V2 sp, V3 contrib) { Add(true, sp, contrib); }                 // GeneratePath: camera side only
 };
+// ... the exact film: the own-pixel sum is three int64 words of unweighted fixed-point contributions
+template <>
+struct McSink<FilmFixed> {
+    FilmFixed film;
+    unsigned long long ax, ay, az;  // two's complement: the unsigned add is the signed one
+    int accPix;
+    unsigned splats;
+    LMC_D void Add(bool ownPixel, V2 sp, V3 contrib) {
+        if (Luminance(contrib) <= kMcMinLuminance) return;
+        if (!AllFinite(contrib)) return;
+        splats++;
+        if (fabsf(contrib.x) >= FILM_FX_LIMIT || fabsf(contrib.y) >= FILM_FX_LIMIT || fabsf(contrib.z) >= FILM_FX_LIMIT) {  // Splat(FilmFixed)'s range rule
+            atomicAdd(film.fx + (size_t)film.W * film.H * 3, 1ull);
+            return;
+        }
+        const unsigned long long qx = (unsigned long long)llrint((double)contrib.x * FILM_FX_SCALE), qy = (unsigned long long)llrint((double)contrib.y * FILM_FX_SCALE),
+                                 qz = (unsigned long long)llrint((double)contrib.z * FILM_FX_SCALE);
+        const int pix = McSink<Film>::PixelOf(Film{nullptr, film.W, film.H}, sp);
+        if (ownPixel && (accPix < 0 || accPix == pix)) {
+            accPix = pix;
+            ax += qx, ay += qy, az += qz;
+            return;
+        }
+        unsigned long long *px = film.fx + (size_t)pix * 3;
+        atomicAdd(px + 0, qx), atomicAdd(px + 1, qy), atomicAdd(px + 2, qz);
+    }
+    LMC_D void Push(const Contrib &c) { Add(c.camDepth != 1, c.screenPos, c.contrib); }
+    LMC_D void operator()(V2 sp, V3 contrib) { Add(true, sp, contrib); }
+};
+LMC_D McSink<Film> MakeSink(const Film &film, int spp) { return McSink<Film>{film, (float)spp, V3{0, 0, 0}, -1, 0u}; }
+LMC_D McSink<FilmFixed> MakeSink(const FilmFixed &film, int) { return McSink<FilmFixed>{film, 0ull, 0ull, 0ull, -1, 0u}; }
 
 LMC_D float WaveSum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -55,7 +95,7 @@ LMC_D float WaveSum(float v) {
 }
 
 // every lane of the wave arrives here (converged): the own-pixel sums of the wave committed, one add per pixel for the lanes that share one
-LMC_D void CommitOwnPixel(const Film &film, McSink &sink, int lane) {
+LMC_D void CommitOwnPixel(const Film &film, McSink<Film> &sink, int lane) {
     const int key = sink.accPix;
     unsigned long long pending = __ballot(key >= 0);
     for (int round = 0; pending && round < 4; round++) {
@@ -88,6 +128,32 @@ LMC_D unsigned long long WaveSumU64(unsigned long long v) {
     return v;
 }
 
+// ... the same rounds over the exact film: the group's three words summed in integers, one lane issues the three 64-bit atomics
+LMC_D void CommitOwnPixel(const FilmFixed &film, McSink<FilmFixed> &sink, int lane) {
+    const int key = sink.accPix;
+    unsigned long long pending = __ballot(key >= 0);
+    for (int round = 0; pending && round < 4; round++) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int lk = __shfl(key, leader);
+        const bool mine = key == lk && key >= 0;
+        const unsigned long long group = __ballot(mine);
+        if (__popcll(group) < 2) break;  // lanes on different pixels: plain atomics below
+        const unsigned long long rx = WaveSumU64(mine ? sink.ax : 0ull), ry = WaveSumU64(mine ? sink.ay : 0ull), rz = WaveSumU64(mine ? sink.az : 0ull);
+        if (lane == leader) {
+            unsigned long long *px = film.fx + (size_t)lk * 3;
+            atomicAdd(px + 0, rx), atomicAdd(px + 1, ry), atomicAdd(px + 2, rz);
+        }
+        if (mine) sink.accPix = -1;
+        pending &= ~group;
+    }
+    if (sink.accPix >= 0) {
+        unsigned long long *px = film.fx + (size_t)sink.accPix * 3;
+        atomicAdd(px + 0, sink.ax), atomicAdd(px + 1, sink.ay), atomicAdd(px + 2, sink.az);
+    }
+    sink.accPix = -1;
+    sink.ax = sink.ay = sink.az = 0ull;
+}
+
 // LMC_MC_MIN_WAVES: the waves per SIMD the register allocation must leave room for.  3 (at most 168 VGPRs): bidirectional renders at 64 spp
 // take 13 % (torus) / 22 % (veach-door) less time than with the free allocation (208 VGPRs, 2 waves) and than 4 (128 VGPRs, more scratch traffic); the
 // unidirectional kernel needs ~150 either way (profiles/r07_mc_ab_*.jsonl, scripts/build_variant.sh)
@@ -96,8 +162,8 @@ LMC_D unsigned long long WaveSumU64(unsigned long long v) {
 #endif
 
 // counters: [paths traced, contributions splatted]
-template <bool GLOSSY, bool BIDIR>
-__global__ void __launch_bounds__(64, LMC_MC_MIN_WAVES) k_mc(DScene S, Film film, int spp, int nXTiles, int nTiles, long long sBase, int nS, long long streamBegin,
+template <bool GLOSSY, bool BIDIR, class FILM>
+__global__ void __launch_bounds__(64, LMC_MC_MIN_WAVES) k_mc(DScene S, FILM film, int spp, int nXTiles, int nTiles, long long sBase, int nS, long long streamBegin,
                                            long long streamEnd, int minDepth, int maxDepth, uint32_t *tabScratch, unsigned long long *counters) {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -118,7 +184,7 @@ __global__ void __launch_bounds__(64, LMC_MC_MIN_WAVES) k_mc(DScene S, Film film
         rng.state = PcgAdvance(rng.s0, 64);    // RNG(seed)'s first state: 64 LCG steps (the table fill) behind S0
     }
     const int nPix = tw * th;
-    McSink sink{film, (float)spp, V3{0, 0, 0}, -1, 0u};
+    McSink<FILM> sink = MakeSink(film, spp);
     LocalStackT<GLOSSY> stk;
     DPath path;
     unsigned paths = 0;
@@ -146,13 +212,25 @@ void LaunchMC(const DScene &S, const Film &film, bool bidirectional, int spp, in
     const int nS = (int)(sLast - sBase + 1);
     const long long nThreads = (long long)nTiles * nS;
     const dim3 grid((unsigned)((nThreads + 63) / 64)), block(64);
-#define LMC_MC_ARGS S, film, spp, nX, nTiles, sBase, nS, streamBegin, streamEnd, minDepth, maxDepth, tabScratch, counters
-    if (S.glossy && bidirectional) hipLaunchKernelGGL((k_mc<true, true>), grid, block, 0, s, LMC_MC_ARGS);
-    else if (S.glossy) hipLaunchKernelGGL((k_mc<true, false>), grid, block, 0, s, LMC_MC_ARGS);
-    else if (bidirectional) hipLaunchKernelGGL((k_mc<false, true>), grid, block, 0, s, LMC_MC_ARGS);
-    else
-        hipLaunchKernelGGL((k_mc<false, false>), grid, block, 0, s, LMC_MC_ARGS);
+#define LMC_MC_ARGS S, f, spp, nX, nTiles, sBase, nS, streamBegin, streamEnd, minDepth, maxDepth, tabScratch, counters
+    DispatchFilm(film, [&](const auto &f) {
+        using FILM = std::decay_t<decltype(f)>;
+        if (S.glossy && bidirectional) hipLaunchKernelGGL((k_mc<true, true, FILM>), grid, block, 0, s, LMC_MC_ARGS);
+        else if (S.glossy) hipLaunchKernelGGL((k_mc<true, false, FILM>), grid, block, 0, s, LMC_MC_ARGS);
+        else if (bidirectional) hipLaunchKernelGGL((k_mc<false, true, FILM>), grid, block, 0, s, LMC_MC_ARGS);
+        else
+            hipLaunchKernelGGL((k_mc<false, false, FILM>), grid, block, 0, s, LMC_MC_ARGS);
+    });
 #undef LMC_MC_ARGS
+}
+// the exact mc film as floats (lmc_mc_read): float(double(q) * 2^-32 / double(spp)), the one division of the exact mode; numpy's
+// np.float32(np.float64(q) * 2.0**-32 / spp) takes the same three steps
+__global__ void k_mc_fixed_to_float(const long long *fx, float *rgb, size_t n, double spp) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) rgb[i] = (float)((double)fx[i] * (1.0 / FILM_FX_SCALE) / spp);
+}
+void LaunchMCFixedToFloat(const long long *fx, float *rgb, size_t n, int spp, hipStream_t s) {
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    if (n) hipLaunchKernelGGL(k_mc_fixed_to_float, dim3(blocks), dim3(256), 0, s, fx, rgb, n, (double)spp);
 }
 long long MCThreads(const DScene &S, long long streamBegin, long long streamEnd) {
     const int nTiles = ((S.cam.width + 15) / 16) * ((S.cam.height + 15) / 16);

@@ -6,7 +6,7 @@
 //         around the render.  The one deliberate deviation: the reference computes this film and writes nothing (pathtrace.cpp:77,
 //         main.cpp:95); dpt_amd writes it like the MLT branch does.  --seedoffset feeds the streams' seed offset (the reference's PathTrace
 //         ignores it; with the default 0 the two agree).  --gpus / --devices split the stream range into contiguous shards, one context
-//         per device, and the films are summed on the host.  The MLT-only flags (--chains, --resident, --init-threads) are ignored.
+//         per device, and the films are summed on member 0's device (lmc_group_mc_render).  The MLT-only flags (--chains, --resident, --init-threads) are ignored.
 //   mcmc  the LMC path: mala = true or h2mc = true; plain MLT (both false) is refused.
 // Extra flags (not in the reference): --chains N (Markov chains resident on the GPUs, default: <dpt numchains>), --init-threads V (MLTInit
 // streams, default 65536), --device D, --force-diffuse, --maxdepth D, --resident K (the resident schedule, lmc_set_option "resident_steps": up to K mutations of every chain per launch once the gradient caches are frozen; H2MC
@@ -23,6 +23,10 @@
 // not depend on the order of the splats -- the same bytes from run to run, for any --gpus / --devices, with or without --resident, and across
 // --checkpoint / --resume.  A resume takes the mode from the file; --exact-film on a float-film checkpoint is an error.  The EXR is produced from the
 // converted float film exactly as in float mode.
+// On an mc scene --exact-film selects the exact mc film (lmc_set_option "mc_film_exact", INTEGRATION.md "Exact mc film"): the same words for any --gpus /
+// --devices list, for any cut into legs, and from run to run.  There --spp N overrides <dpt spp>, --max-spp K renders the sample indices below K only
+// and writes the image with divisor K, --checkpoint F writes the film's state file (lmc_mc_save) at the end and --resume F loads one and renders what
+// its coverage lacks of [0, nTiles * spp); both need the exact film (a resume takes the mode from the file).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -50,41 +54,96 @@ static double Opt(lmc_ctx *ctx, const char *name) {
     return v;
 }
 
-// integrator = mc: the stream range [0, nTiles * spp) split into contiguous shards, one per context, rendered concurrently
-static int RenderMC(const std::string &filename, const std::vector<lmc_ctx *> &ctxs) {
+// the mc branch's flags
+struct McFlags {
+    bool exactFilm = false;
+    int spp = 0, maxSpp = 0;  // --spp / --max-spp (0: not given)
+    std::string checkpointPath, resumePath;
+};
+
+// integrator = mc: the stream range [0, nTiles * spp) split into contiguous shards, one per context, rendered concurrently and summed on member 0's
+// device (lmc_group_mc_render).  With --max-spp K only the sample indices below K are rendered and the image is written with divisor K; --resume
+// renders what the file's coverage lacks of that range.
+static int RenderMC(const std::string &filename, std::vector<lmc_ctx *> &ctxs, const McFlags &F) {
     lmc_ctx *ctx = ctxs[0];
     int info[8];
     lmc_info(ctx, info);
-    const int W = info[0], H = info[1], spp = (int)Opt(ctx, "spp"), nDev = (int)ctxs.size();
-    const long long total = (long long)((W + 15) / 16) * ((H + 15) / 16) * spp;
-    if (nDev > 1) printf("%lld sample streams sharded over %d devices\n", total, nDev);
-    std::vector<int> rc(nDev, 0);
-    std::vector<std::string> err(nDev);  // lmc_last_error is per thread
-    auto t0 = std::chrono::steady_clock::now();
-    std::vector<std::thread> th;
-    for (int k = 0; k < nDev; k++)
-        th.emplace_back([&, k] {
-            rc[k] = lmc_mc_render(ctxs[k], spp, total * k / nDev, total * (k + 1) / nDev);
-            if (rc[k] != 0) err[k] = lmc_last_error();
-        });
-    for (auto &t : th) t.join();
-    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int k = 0; k < nDev; k++)
-        if (rc[k] != 0) {
-            fprintf(stderr, "%s\n", err[k].c_str());
-            return 1;
-        }
-    printf("Elapsed time:%g\n", elapsed);  // pathtrace.cpp:74-75
-    std::vector<float> img((size_t)W * H * 3, 0.0f), part((size_t)W * H * 3);
-    long long paths = 0, splats = 0;
-    for (lmc_ctx *c : ctxs) {
-        long long st[2];
-        if (lmc_mc_read(c, part.data()) != 0 || lmc_mc_stats(c, st) != 0) {
+    const int W = info[0], H = info[1], sceneSpp = F.spp > 0 ? F.spp : (int)Opt(ctx, "spp"), nDev = (int)ctxs.size();
+    const int spp = F.maxSpp > 0 ? std::min(F.maxSpp, sceneSpp) : sceneSpp;  // what this invocation's film ends with, and its divisor
+    const long long nTiles = (long long)((W + 15) / 16) * ((H + 15) / 16), total = nTiles * spp;
+    bool exact = F.exactFilm || Opt(ctx, "mc_film_exact") != 0;
+    if (!F.resumePath.empty()) {  // a resume takes the mode from the file: a state file holds an exact film
+        char json[4096];
+        if (lmc_mc_file_info(F.resumePath.c_str(), json, sizeof(json)) < 0) {
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
         }
-        for (size_t i = 0; i < img.size(); i++) img[i] += part[i];
-        paths += st[0], splats += st[1];
+        exact = true;
+    }
+    if (!exact && (!F.checkpointPath.empty() || !F.resumePath.empty())) {
+        fprintf(stderr, "--checkpoint / --resume on an integrator=mc scene need the exact film: add --exact-film\n");
+        return 2;
+    }
+    for (lmc_ctx *c : ctxs)
+        if (lmc_set_option(c, "mc_film_exact", exact ? 1 : 0) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+    if (exact) printf("Exact film: 64-bit fixed-point accumulation\n");
+    if (nDev > 1) printf("%lld sample streams sharded over %d devices\n", total, nDev);
+    auto t0 = std::chrono::steady_clock::now();
+    if (F.resumePath.empty()) {
+        if (lmc_group_mc_render(ctxs.data(), nDev, spp, 0, total) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+    } else {
+        if (lmc_mc_load(ctx, F.resumePath.c_str()) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+        std::vector<long long> held(2 * 4096);
+        const int nHeld = lmc_mc_coverage(ctx, held.data(), 4096);
+        if (nHeld < 0 || nHeld > 4096) {
+            fprintf(stderr, "%s\n", nHeld < 0 ? lmc_last_error() : "--resume: the file's coverage has more than 4096 ranges");
+            return 1;
+        }
+        if (nHeld > 0 && held[2 * nHeld - 1] > total) {
+            fprintf(stderr, "--resume: %s holds stream ids beyond the %lld of %d spp\n", F.resumePath.c_str(), total, spp);
+            return 2;
+        }
+        long long at = 0, rendered = 0;
+        for (int k = 0; k <= nHeld && at < total; k++) {  // the gaps of the coverage within [0, total)
+            const long long gapEnd = k < nHeld ? std::min(held[2 * k], total) : total;
+            if (gapEnd > at) {
+                if (lmc_group_mc_accumulate(ctxs.data(), nDev, spp, at, gapEnd) != 0) {
+                    fprintf(stderr, "%s\n", lmc_last_error());
+                    return 1;
+                }
+                rendered += gapEnd - at;
+            }
+            if (k < nHeld) at = std::max(at, held[2 * k + 1]);
+        }
+        if (rendered == 0 && lmc_mc_accumulate(ctx, spp, 0, 0) != 0) {  // nothing was missing: the divisor is still this invocation's
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+        printf("Resumed from %s: %lld of %lld sample streams were missing\n", F.resumePath.c_str(), rendered, total);
+    }
+    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("Elapsed time:%g\n", elapsed);  // pathtrace.cpp:74-75
+    std::vector<float> img((size_t)W * H * 3, 0.0f);
+    long long st[2] = {0, 0}, dropped = 0;
+    if (lmc_mc_read(ctx, img.data()) != 0 || lmc_mc_stats(ctx, st) != 0 || lmc_mc_overflow(ctx, &dropped) != 0) {
+        fprintf(stderr, "%s\n", lmc_last_error());
+        return 1;
+    }
+    if (!F.checkpointPath.empty()) {
+        if (lmc_mc_save(ctx, F.checkpointPath.c_str()) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+        printf("Checkpoint written to %s (%d spp)\n", F.checkpointPath.c_str(), spp);
     }
     std::string dir = filename.rfind('/') != std::string::npos ? filename.substr(0, filename.rfind('/') + 1) : "";
     std::string out = dir + lmc_output_name(ctx) + "_timeuse_" + std::to_string(elapsed) + "s.exr";
@@ -92,7 +151,8 @@ static int RenderMC(const std::string &filename, const std::vector<lmc_ctx *> &c
         fprintf(stderr, "%s\n", lmc_last_error());
         return 1;
     }
-    printf("%lld paths, %lld contributions, %.1f M paths/s, wrote %s\n", paths, splats, paths / elapsed * 1e-6, out.c_str());
+    if (dropped > 0) printf("Exact film: %lld contributions with a component of 2^30 or more were dropped\n", dropped);
+    printf("%lld paths, %lld contributions, %.1f M paths/s, wrote %s\n", st[0], st[1], st[0] / elapsed * 1e-6, out.c_str());
     return 0;
 }
 
@@ -103,6 +163,7 @@ int main(int argc, char *argv[]) {
     long long chains = 0, maxSteps = -1, checkpointEvery = 0;
     std::string checkpointPath, resumePath;
     bool exactFilm = false;
+    int mcSpp = 0, mcMaxSpp = 0;  // --spp / --max-spp (integrator = mc)
     bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -135,6 +196,8 @@ int main(int argc, char *argv[]) {
         else if (a == "--max-steps") maxSteps = std::stoll(argv[++i]);
         else if (a == "--resume") resumePath = argv[++i];
         else if (a == "--exact-film") exactFilm = true;
+        else if (a == "--spp") mcSpp = std::stoi(argv[++i]);
+        else if (a == "--max-spp") mcMaxSpp = std::stoi(argv[++i]);
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -163,7 +226,9 @@ int main(int argc, char *argv[]) {
         lmc_ctx *ctx = ctxs[0];
         if (Opt(ctx, "integrator_mc") != 0) {  // main.cpp:92-96
             if (mltFlags) printf("--chains / --resident / --init-threads: ignored by integrator=mc\n");
-            const int rc = RenderMC(filename, ctxs);
+            McFlags mf;
+            mf.exactFilm = exactFilm, mf.spp = mcSpp, mf.maxSpp = mcMaxSpp, mf.checkpointPath = checkpointPath, mf.resumePath = resumePath;
+            const int rc = RenderMC(filename, ctxs, mf);
             for (lmc_ctx *c : ctxs) lmc_destroy(c);
             if (rc != 0) return rc;
             printf("Done!\n");
