@@ -82,8 +82,8 @@ void LaunchStepSmallLeanGrad(const lmcd::DScene &S, const lmcd::DCache *cache, c
                              const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed,
                              hipStream_t s);
 void LaunchStepSmallPlain(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P,
-                          const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads,
-                          bool profile, hipStream_t s);
+                          const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads,
+                          bool profile, hipStream_t s);  // one chain per thread: the grid is A.N slots; ldsStack = false: the private-stack instantiations whatever the tree
 // the resident schedule (step_resident.h / .hip): every chain of the slot arrays advances by up to maxSteps complete mutations in ONE launch (caches frozen);
 // lanes = active chains per 64-lane wave (16 / 32 / 64); guard[0] += chain-steps run, guard[1] += steps that would have needed the gradient program or a cache push
 void LaunchStepResident(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P, int maxSteps,

@@ -11,17 +11,18 @@ template <class FILM>
 static void LaunchStepLargeMuxT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
                      const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {
     RequireJumpLdsBlock(blockThreads);
+    const StepKernArgs<FILM> K{S, cache, A, film, P, list, listCount, gradBuf, gradStride, 0};
     if (bvhStackNeed <= BVH_LDS_STACK) {  // traversal stack in LDS; gridBlocks was sized for 256-thread blocks
         const int blocks = gridBlocks * (256 / blockThreads);
         const size_t ldsBytes = (size_t)blockThreads * ((bvhStackNeed + 7) / 8 * 8) * sizeof(int);  // the scene's own stack need, not the cap
-        if (glossy) hipLaunchKernelGGL((k_step<FILM, true, false, false, true, true, 1>), dim3(blocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+        if (glossy) LaunchKernArgs(k_step<FILM, true, false, false, true, true, 1>, dim3(blocks), dim3(blockThreads), ldsBytes, s, K);
         else
-            hipLaunchKernelGGL((k_step<FILM, true, false, false, false, true, 1>), dim3(blocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+            LaunchKernArgs(k_step<FILM, true, false, false, false, true, 1>, dim3(blocks), dim3(blockThreads), ldsBytes, s, K);
         return;
     }
-    if (glossy) hipLaunchKernelGGL((k_step<FILM, true, false, false, true, false, 1>), dim3(gridBlocks), dim3(256), 0, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+    if (glossy) LaunchKernArgs(k_step<FILM, true, false, false, true, false, 1>, dim3(gridBlocks), dim3(256), 0, s, K);
     else
-        hipLaunchKernelGGL((k_step<FILM, true, false, false, false, false, 1>), dim3(gridBlocks), dim3(256), 0, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+        LaunchKernArgs(k_step<FILM, true, false, false, false, false, 1>, dim3(gridBlocks), dim3(256), 0, s, K);
 }
 void LaunchStepLargeMux(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
                      const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {

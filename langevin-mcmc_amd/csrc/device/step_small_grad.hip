@@ -9,7 +9,8 @@ template <class FILM>
 static void LaunchStepSmallGradT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
                          const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, hipStream_t s) {
     (void)glossy;
-    hipLaunchKernelGGL((k_step<FILM, false, true, true, true>), dim3(gridBlocks), dim3(256), 0, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride);
+    const StepKernArgs<FILM> K{S, cache, A, film, P, list, listCount, gradBuf, gradStride, 0};
+    LaunchKernArgs(k_step<FILM, false, true, true, true>, dim3(gridBlocks), dim3(256), 0, s, K);
 }
 void LaunchStepSmallGrad(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
                          const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, hipStream_t s) {

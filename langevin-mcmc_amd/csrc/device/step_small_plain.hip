@@ -29,9 +29,16 @@ template <class FILM, bool USE_LDS_STACK, bool GLOSSY, bool PROF = false, bool L
 // Lambertian one 5 % (it has no registers to give), so they stay at two.
 #define LMC_LEAN_WAVES_GLOSSY_LIGHTLESS 3
 #endif
-__global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GLOSSY_LIGHTLESS : LMC_LEAN_WAVES) k_step_small(DScene S, const DCache *cache, ChainArrays A, FILM film, StepParams P, const int *list,
-                                                    const int *listCount, NextLists next, int stackWords) {
+__global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GLOSSY_LIGHTLESS : LMC_LEAN_WAVES) k_step_small(StepKernArgs<FILM> /* read through KernArgs (step_kernel.h) */) {
     extern __shared__ float lds[];
+    const StepKernArgs<FILM> &K = KernArgs<StepKernArgs<FILM>>();
+    const DScene &S = K.S;
+    const DCache *cache = K.cache;
+    const ChainArrays &A = K.A;
+    const FILM &film = K.film;
+    const StepParams &P = K.P;
+    const int *list = K.list, *listCount = K.listCount;
+    const int stackWords = K.stackWords;
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
     LMC_RNG_JUMP_INIT();
     LMC_MAT_LDS_INIT(S);
@@ -41,7 +48,10 @@ __global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GL
     const LdsView L{lds + threadIdx.x, (int)blockDim.x, stackWords};
     typename std::conditional<PROF, WaveProf, NoProf>::type prof;
     if constexpr (PROF) prof.Start();
-    for (int j = tid; j < total; j += gridDim.x * blockDim.x) {
+    // One chain per thread, no grid-stride loop: the launch function sizes the grid to cover every slot a list can name.  Around a loop the compiler hoists every
+    // launch-uniform value of the body (addresses of the chain arrays, scene constants) in front of it and keeps them alive, or spilled, through the whole
+    // step: the loop alone cost the flagship instantiation 31 VGPRs and all of its VGPR spills.
+    if (const int j = tid; j < total) {
         const int i = list[j];
         Rng rng = LoadChainRng(A, P.chainBegin, S.opt.seedOffset, i);
 #if LMC_LEAN_K > 1  // A/B build (DESIGN.md "K small steps of a chain per launch"): the chain stays in its lane for up to K consecutive plain small steps
@@ -76,13 +86,15 @@ __global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS) ? LMC_LEAN_WAVES_GL
 
 template <class FILM>
 static void LaunchStepSmallPlainT(const DScene &S, const DCache *cache, const ChainArrays &A, const FILM &film, const StepParams &P, const int *list, const int *listCount,
-                          const NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads, bool profile, hipStream_t s) {
+                          const NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads, bool profile, hipStream_t s) {
     RequireJumpLdsBlock(blockThreads);
+    const int gridBlocks = (A.N + blockThreads - 1) / blockThreads;  // the kernel runs one chain per thread: the grid covers every slot a list can name
     const int stackWords = LeanStackWords(bvhDepth);  // bvhDepth: the tree's stack need (host/accel.cpp)
     size_t ldsBytes = (size_t)blockThreads * LeanLdsWordsPerThread(stackWords) * sizeof(float);
     if (const char *e = getenv("LMC_EXP_LDS_EXTRA")) ldsBytes += (size_t)atoi(e);  // measurement aid: lowers the occupancy without touching the code
-    const bool lds = bvhDepth <= BVH_LDS_STACK;
-#define LMC_LAUNCH_SMALL(...) hipLaunchKernelGGL((k_step_small<FILM, __VA_ARGS__>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, stackWords)
+    const bool lds = ldsStack && bvhDepth <= BVH_LDS_STACK;  // ldsStack = false (LMC_LEAN_LDS=0, host/context.cpp): the private-stack fallback on a tree that would fit
+    const StepKernArgs<FILM> K{S, cache, A, film, P, list, listCount, nullptr, 0, stackWords};
+#define LMC_LAUNCH_SMALL(...) LaunchKernArgs(k_step_small<FILM, __VA_ARGS__>, dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, K)
     const bool quant = S.qnodes != nullptr && lds && !profile;  // the scene's choice (host/context.cpp UploadScene); the profiling and fallback instantiations stay on the exact nodes
     if (profile && lds && glossy) LMC_LAUNCH_SMALL(true, true, true);
     else if (profile && lds && !glossy) LMC_LAUNCH_SMALL(true, false, true);
@@ -109,6 +121,6 @@ static void LaunchStepSmallPlainT(const DScene &S, const DCache *cache, const Ch
 #undef LMC_LAUNCH_SMALL
 }
 void LaunchStepSmallPlain(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
-                          const NextLists &next, int bvhDepth, bool glossy, int gridBlocks, int blockThreads, bool profile, hipStream_t s) {
-    DispatchFilm(film, [&](const auto &f) { LaunchStepSmallPlainT(S, cache, A, f, P, list, listCount, next, bvhDepth, glossy, gridBlocks, blockThreads, profile, s); });
+                          const NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads, bool profile, hipStream_t s) {
+    DispatchFilm(film, [&](const auto &f) { LaunchStepSmallPlainT(S, cache, A, f, P, list, listCount, next, bvhDepth, glossy, ldsStack, blockThreads, profile, s); });
 }

@@ -114,6 +114,7 @@ struct lmc_ctx {
     bool useOccFilter = true;  // LMC_OCC_FILTER=0: A/B switch for the existence test in front of the cache query
     int gridDims = 4;          // LMC_GRID_DIMS: rank of its grid (3 or 4)
     bool largeLdsStack = true;  // LMC_LARGE_LDS=0: A/B switch for the LDS traversal stack of the large-step launch
+    bool leanLdsStack = true;   // LMC_LEAN_LDS=0: the lean launch on its private-stack instantiations (the fallback of trees deeper than BVH_LDS_STACK) whatever the tree
     int largeBlock = 64;        // LMC_LARGE_BLOCK: its block size (64, 128 or 256); 128 disturbs the lean launch less (its bracket 2.4 instead of 2.7 ms) but the step and the start-up end 1-2 % later (profiles/r02_j_ab_block_sizes.jsonl)
     bool leanGrad = true;      // LMC_LEAN_GRAD=0: the cache-filling launch falls back to k_step<false,true,true,true>
     bool anyDeepCache = false;  // (always false since the LDS search is gone: see DCacheDim::deep)
@@ -218,7 +219,7 @@ struct lmc_ctx {
     int gradStride = 0, stepGrid = 0;
     // launch shape of the lean small-step kernel and the technique sort of its work list; LMC_LEAN_BLOCK / LMC_SORT_PLAIN
     // override them for A/B runs (profiles/)
-    int leanBlock = 64, leanGrid = 0, sortPlain = 0;
+    int leanBlock = 64, sortPlain = 0;  // (the lean launch runs one chain per thread: its launch function sizes the grid, step_small_plain.hip)
     // chain relocation (device/relocate.hip): the chains kept physically grouped by technique from the first step on (fill phase included: the safety argument is at the launch site, StepPhase1); LMC_RELOCATE overrides
     bool relocate = false;
     DevBuf<int> chainId, slotOf, relocTileCount, relocTileHist, relocMembers, relocSorted, relocCount;
@@ -589,6 +590,7 @@ lmc_ctx *lmc_create(const lmc_scene_desc *desc) {
     if (const char *e = getenv("LMC_OVERLAP")) c->overlap = atoi(e) != 0;
     if (const char *e = getenv("LMC_OCC_FILTER")) c->useOccFilter = atoi(e) != 0;
     if (const char *e = getenv("LMC_LARGE_LDS")) c->largeLdsStack = atoi(e) != 0;
+    if (const char *e = getenv("LMC_LEAN_LDS")) c->leanLdsStack = atoi(e) != 0;
     if (const char *e = getenv("LMC_LARGE_BLOCK")) c->largeBlock = atoi(e) == 64 ? 64 : atoi(e) == 128 ? 128 : 256;
     if (const char *e = getenv("LMC_PROF")) c->profileLean = atoi(e) != 0;
     if (const char *e = getenv("LMC_LEAN_GRAD")) c->leanGrad = atoi(e) != 0;
@@ -1215,7 +1217,8 @@ void SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
         LaunchSeedRng((int)N, (long long)chainBegin + c->S.opt.seedOffset, c->rngState.p, c->rngTab.p, s);  // RNG rng(chainId + seedOffset), mlt.cpp:61-62
         LaunchSetupChains(A, chainBegin, perChain, chainsNeedExtra, s);
     }
-    // step launch geometry: one thread per chain up to a persistent cap; gradient work buffer per launched thread
+    // step launch geometry of the large-step and generic launches: one thread per chain up to a persistent cap; gradient work buffer per launched thread
+    // (the lean launch has no cap: one chain per thread, grid sized by its launch function)
     c->stepGrid = (int)std::min<size_t>((N + 255) / 256, 4096);
     c->gradStride = c->stepGrid * 256;
     if (const char *e = getenv("LMC_LEAN_BLOCK")) c->leanBlock = std::max(64, std::min(256, atoi(e) / 64 * 64));
@@ -1226,7 +1229,6 @@ void SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     // LMC_SORT_PLAIN overrides: 0 | 1 (1024-chain tiles) | 2 (256-chain tiles) | 3 (two classes) | 4 (whole list)
     c->sortPlain = c->S.glossy ? 4 : 0;
     if (const char *e = getenv("LMC_SORT_PLAIN")) c->sortPlain = atoi(e);
-    c->leanGrid = (int)std::min<size_t>((N + c->leanBlock - 1) / c->leanBlock, (size_t)4096 * 256 / c->leanBlock);
     c->gradBuf.Alloc(c->useGradient ? (size_t)c->gradStride * 640 : 1, false);  // V <= 238 + 59*6 = 592 words for c+l <= 9
     // global cache: dims 2L for L in [3, maxDepth], capped by PSS_MAX_LENGTH
     size_t maxGridCells = 0;
@@ -1953,7 +1955,7 @@ bool StepPhase1(lmc_ctx *c, lmc_ctx::StepEvents &ev) {
     if (c->timing) HIP_CHECK(hipEventRecord(ev.e[1], s));
     // every small step of an H2MC render runs the pipeline: the lean list is empty by construction (QueueNext, LeanDims), and its launch of
     // four-wave blocks sat in the queue for the length of the large-step launch
-    if (!c->S.opt.h2mc) LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanGrid, c->leanBlock, c->profileLean, s);
+    if (!c->S.opt.h2mc) LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
     if (c->timing) HIP_CHECK(hipEventRecord(ev.e[2], s));
     if (c->overlap) {
         HIP_CHECK(hipEventRecord(c->joinEvent[0], sL));
@@ -2070,7 +2072,7 @@ static void WarmStepLaunches(lmc_ctx *c) {
         LaunchGeneric(c, film, P, 0, cnt, next, sG);
         c->allCachesReady = false;
     }
-    LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[0][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanGrid, c->leanBlock, c->profileLean, s);
+    LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[0][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
     HIP_CHECK(hipStreamSynchronize(sL));
     HIP_CHECK(hipStreamSynchronize(sG));
     HIP_CHECK(hipStreamSynchronize(s));
