@@ -1,4 +1,4 @@
-// Checkpoint records (host/context.cpp lmc_checkpoint_save / _load; INTEGRATION.md "Checkpoint and resume"): every word the chain loop can read of a
+// Checkpoint records (host/ckpt.cpp lmc_checkpoint_save / _load; INTEGRATION.md "Checkpoint and resume"): every word the chain loop can read of a
 // chain between two steps, as ONE record per chain in chain order -- whatever slot the chain lives in (relocate.hip) and whatever member of an
 // in-process group holds it.  The relocation's staging record (relocate.hip RW_*) is the model; added here: the chain's init state (the outlier
 // reset reads it, dchain.h ResetToInitState), `samplecache`'s chain.path / chain.spContrib and the dense Gaussian of an H2MC chain

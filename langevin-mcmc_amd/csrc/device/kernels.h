@@ -1,4 +1,4 @@
-// Launch entry points of kernels.hip (compiled by hipcc for gfx950); called from host/context.cpp.
+// Launch entry points of kernels.hip (compiled by hipcc for gfx950); called from host/context.cpp and the units beside it (ckpt.cpp, mcrender.cpp, probes.cpp, plugin_abi.cpp, list_probes.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

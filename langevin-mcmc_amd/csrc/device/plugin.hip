@@ -1,5 +1,5 @@
 // The reference's plugin ABI, ONE evaluation per call (evaluate_path_bidir_mala_<c>_<l>_static{,_derv}; caller mutation_mala.h:97-110):
-// a single wave.  The caller's arrays arrive through host-mapped pinned memory and the result leaves the same way (host/context.cpp
+// a single wave.  The caller's arrays arrive through host-mapped pinned memory and the result leaves the same way (host/plugin_abi.cpp
 // PluginSlot: no hipMalloc, no copy call, one launch + one stream sync per call); the wave stages the inputs in LDS and lane k computes
 // d logLum / d primary[k + 1] with a one-wide dual number -- the gradient's components side by side instead of one after the other.
 #include "kernels.h"

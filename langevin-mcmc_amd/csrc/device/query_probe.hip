@@ -1,4 +1,4 @@
-// Test probe (host/context.cpp lmc_lean_query_probe): the lean small step's cache look-up -- dsmall.h PrepareGaussianLean and GaussianDim as they
+// Test probe (host/probes.cpp lmc_lean_query_probe): the lean small step's cache look-up -- dsmall.h PrepareGaussianLean and GaussianDim as they
 // stand, called the way SmallStepLean calls them for a proposal -- on caller-given cache rows and chain states, one query per lane, with the LDS laid
 // out as the lean launch lays it out (LdsView, the query in L.Q).  Next to it the generic kernel's CacheQuery (dchain.h) on the same query.
 // The stand-in ChainArrays of N = nq hold only the words the two functions touch: pathWeight, chV1, chV2, chLastPss.

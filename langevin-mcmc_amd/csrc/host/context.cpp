@@ -1,6 +1,8 @@
 // C-ABI implementation (include/lmc_abi.h): scene upload, MLT initialisation, the chain-step loop and the
 // global-cache maintenance around the gfx950 kernels.  Host logic only -- every numeric result returned by this
 // library is produced by the HIP kernels in device/kernels.hip; there is no CPU fallback.
+// The cold parts of the ABI live in units of their own beside this one: checkpoints (ckpt.cpp), the mc and direct-lighting passes (mcrender.cpp),
+// the probes and batch calls (probes.cpp, list_probes.cpp), the reference's plugin symbols (plugin_abi.cpp).  context.h is what they see of this unit.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -28,315 +30,22 @@
 #include "../device/dh2coop.h"
 #include "../device/dh2mc.h"
 #include "accel.h"
-#include "last_error.h"
+#include "context.h"
+#include "hostutil.h"
 #include "scene.h"
-#include "mcfilm.h"
 #include "shardplan.h"
 
 using namespace lmcd;
 
 static thread_local std::string g_err;
 
-#define HIP_CHECK(x)                                                                                                  \
-    do {                                                                                                              \
-        hipError_t e_ = (x);                                                                                          \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-    } while (0)
-
-namespace {
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DevBuf() {}
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { Free(); }
-    void Free() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    void Alloc(size_t count, bool zero = true) {
-        Free();
-        n = count;
-        if (count == 0) return;
-        HIP_CHECK(hipMalloc((void **)&p, count * sizeof(T)));
-        if (zero) HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
-    }
-    void Upload(const std::vector<T> &v) {
-        Alloc(v.size(), false);
-        if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    }
-    void Upload(const T *v, size_t count) {
-        Alloc(count, false);
-        if (count) HIP_CHECK(hipMemcpy(p, v, count * sizeof(T), hipMemcpyHostToDevice));
-    }
-    std::vector<T> Download() const {
-        std::vector<T> v(n);
-        if (n) HIP_CHECK(hipMemcpy(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost));
-        return v;
-    }
-};
-
-void EnsureDevice(int device) {
+void lmc_host::EnsureDevice(int device) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) throw std::runtime_error("no HIP device available: the MI355X back end has no CPU fallback");
     if (device < 0 || device >= count) throw std::runtime_error("HIP device ordinal out of range");
     HIP_CHECK(hipSetDevice(device));
 }
-
-struct CacheDimHost {
-    DevBuf<float> pss, v1, v2, weight;
-    DevBuf<float> extra, distCdf;  // `samplecache`: the rows' paths + contributions (CACHE_ROW_EXTRA words each), PiecewiseConstant1D over the weights
-    DevBuf<KdNode> nodes;
-    DevBuf<uint2> gridWords;           // the compact existence grid (dchain.h DCacheDim): occupancy words + ranks,
-    DevBuf<int> gridCellStart;         // the candidate range of every non-empty cell,
-    DevBuf<unsigned short> gridIdx;    // the candidates' row indices
-    int gridG = 0, gridM = 0;
-    int gridCoord[4] = {0, 1, 2, 3};  // the coordinates the grid is laid over, chosen from the rows when the dim becomes ready (accel.h ChooseGridCoords)
-    DevBuf<int> vind;
-    bool ready = false;
-    bool relevant = false;
-};
-
-}  // namespace
-
-static int GetRcclDestroy(void *comm);  // RCCL is bound lazily (below)
-
-struct lmc_ctx {
-    std::unique_ptr<lmc::Scene> scene;
-    int device = 0;
-    int useGradient = 1;
-    int maxDervDepth = 8;  // --max-derivatives-depth default, main.cpp:46
-    bool useOccFilter = true;  // LMC_OCC_FILTER=0: A/B switch for the existence test in front of the cache query
-    int gridDims = 4;          // LMC_GRID_DIMS: rank of its grid (3 or 4)
-    bool largeLdsStack = true;  // LMC_LARGE_LDS=0: A/B switch for the LDS traversal stack of the large-step launch
-    bool leanLdsStack = true;   // LMC_LEAN_LDS=0: the lean launch on its private-stack instantiations (the fallback of trees deeper than BVH_LDS_STACK) whatever the tree
-    int largeBlock = 64;        // LMC_LARGE_BLOCK: its block size (64, 128 or 256); 128 disturbs the lean launch less (its bracket 2.4 instead of 2.7 ms) but the step and the start-up end 1-2 % later (profiles/r02_j_ab_block_sizes.jsonl)
-    bool leanGrad = true;      // LMC_LEAN_GRAD=0: the cache-filling launch falls back to k_step<false,true,true,true>
-    bool anyDeepCache = false;  // (always false since the LDS search is gone: see DCacheDim::deep)
-    bool sortH2mc = true;
-    bool sortGeneric = true;   // LMC_SORT_GENERIC=0: A/B switch for the technique sort of the cache-filling launch
-    DevBuf<int> listScratch, listScratch2, sortBins, sortBins2;
-    int expFlags = 0;      // LMC_EXP_NOSPLAT / LMC_EXP_NOQUERY: measurement aids (dstep_params.h)
-    hipStream_t stream = nullptr;
-    // The three step launches of one iteration touch disjoint chains, so they run concurrently: large steps and the generic
-    // (gradient) small steps on two side streams, the lean small steps on the main stream, joined before k_build_lists.
-    // LMC_OVERLAP=0 serialises them on the main stream (A/B).
-    hipStream_t sideStream[2] = {nullptr, nullptr};
-    static constexpr int H2_MAX_PARTS = 4;
-    hipStream_t partStream[H2_MAX_PARTS - 1] = {};  // H2MC: the pipelines of the other parts of the chain population (LaunchGeneric)
-    hipEvent_t partFork = nullptr, partJoin[H2_MAX_PARTS - 1] = {};
-    hipEvent_t h2HeadDone[H2_MAX_PARTS] = {};  // H2MC: behind each part's k_h2_begin (the large-step launch can be made to wait for them: LMC_H2_LARGE_AFTER)
-    int h2HeadParts = 0;
-    hipEvent_t forkEvent = nullptr, joinEvent[2] = {nullptr, nullptr};
-    hipEvent_t packedEvent = nullptr, copiedEvent = nullptr;  // in-process group: this member's stage is complete / this member has copied every stage (ExchangeStagesAsync)
-    // in-process group, film merge (lmc_group_film_reduce): staging for the slices pulled from the peers + the peers' weight sums, allocated when the
-    // group is set up (nothing is allocated inside the merge); events: this member's film is final / this member's slice holds the sum
-    DevBuf<float> filmStage;
-    DevBuf<long long> filmStageFx;  // ... in exact mode (sized for the mode when the group is set up)
-    DevBuf<double> weightStage;
-    hipEvent_t filmReadyEvent = nullptr, sliceReducedEvent = nullptr, weightsCopiedEvent = nullptr;
-    int groupPeerPairs = 0, groupPeerEnabled = 0, groupDevices = 0;  // ordered pairs of distinct member devices / ... with direct peer access enabled (lmc_group_info)
-    // host time spent queueing the launches of this member's steps (StepPhase1 + exchange + StepPhase2) and the steps it covers (lmc_host_issue_timing)
-    double hostIssueMs = 0;
-    long long hostIssueSteps = 0;
-    DevBuf<double> commScratch;  // RCCL job: device words of lmc_comm_allreduce_f64 / lmc_comm_barrier, allocated by lmc_comm_init
-    bool overlap = true;
-    // scene buffers
-    DevBuf<BvhNode4> nodes;
-    DevBuf<BvhNode4Q> qnodes;
-    double thickFlatShare = 0;  // accel.h ThickenedFlatLeafShare of the scene's tree: decides the node format of the hot launches (UploadScene)
-    DevBuf<LeafTri> leafTris;
-    DevBuf<int> leafPosOfTri;
-    DevBuf<TriData> tris;
-    DevBuf<DMesh> meshes;
-    DevBuf<DMaterial> materials;
-    DevBuf<DBitmap> bitmaps;
-    DevBuf<float> texPool;  // the texels of every bitmap, back to back
-    DevBuf<DLight> lights;
-    DevBuf<float> areaFunc, areaCdf, lightFunc, lightCdf, envImage, envCdfRows, envCdfCols, envRowWeights;
-    DScene S;
-    int bvhDepth = 0;
-    // film
-    DevBuf<float> film, directFilm;
-    // exact mode ("film_exact", INTEGRATION.md "Exact film"): the MLT splats go to filmFx, W*H*3 signed 64-bit fixed-point words (unit 2^-32) followed by
-    // the film_overflow counter; `film` then only receives the converted floats of lmc_film_read.  directFilm and mcFilm stay float in either mode.
-    DevBuf<long long> filmFx;
-    bool filmExact = false;
-    DevBuf<float> mcFilm;                   // lmc_mc_render's film (the mc integrator), weighted by 1 / spp
-    DevBuf<unsigned long long> mcCounters;  // [paths traced, contributions splatted] of the last lmc_mc_render (exact mode: since the film was last cleared)
-    // exact mode of the mc film ("mc_film_exact", INTEGRATION.md "Exact mc film"): the contributions go unweighted to mcFilmFx, W*H*3 fixed-point words followed
-    // by the overflow counter; mcFilm then only receives lmc_mc_read's converted floats, divided by mcDivisor (the spp of the last render / accumulate call)
-    DevBuf<long long> mcFilmFx;
-    bool mcExactOpt = false;   // the option: read by the next lmc_mc_render / lmc_mc_accumulate / lmc_mc_load
-    bool mcFilmIsExact = false;  // the mode of the film the context holds
-    int mcDivisor = 0;
-    lmc::McCoverage mcCoverage;  // the stream ids mcFilmFx holds
-    long long mcLaunchStreams = 262144;  // "mc_launch_streams": stream ids per launch of a render / accumulate call, either mode
-    int mcLaunches = 0;                  // "mc_launches": launches of the last such call
-    int world = 1, rank = 0;          // position in the job (lmc_comm_init: RCCL ranks; lmc_group_chains_init: in-process group)
-    std::vector<lmc_ctx *> group;    // in-process group this context is a member of (empty / 1: none)
-    bool filmReduced = false;  // the device film + weightSum already hold the all-reduced sums (lmc_film_allreduce is in place)
-    void *comm = nullptr;  // ncclComm_t of lmc_comm_init (multi-GPU: one process per GPU, chains sharded by id range)
-    // chains
-    int N = 0, numChainsTotal = 0, chainBegin = 0;
-    // the job's shape as lmc_chains_init was given it, the steps asked for since and the render's wall time before this process took it over: what a
-    // checkpoint's header carries besides the fingerprint (lmc_checkpoint_save / _load)
-    int forceDiffuse = 0, initThreads = 0;
-    long long numInitSamples = 0, perChain = 0, chainsNeedExtra = 0, stepsDone = 0;
-    double secondsBefore = 0;
-    std::chrono::steady_clock::time_point chainsSince;  // when lmc_chains_init / lmc_checkpoint_load left the chains ready
-    unsigned long long sceneHash = 0;                    // content hash of the scene's files, computed by the first save / load
-    ChainArrays A;
-    DevBuf<uint64_t> rngState;
-    DevBuf<uint32_t> rngTab;
-    DevBuf<unsigned char> rngTicked;
-    DevBuf<float> curPath, pathBuf1, curContrib, scoreSum, gaussian, gaussian1, curSplat, chV1, chV2, chCurrNewV2, chPropNewV1, chPropNewV2, chPss, chLastPss, chPath, chContrib, pathWeight,
-        lastScoreSum, lastScore, contribList, pushData, initPath, initContrib, initScoreSum, initLsAll;
-    DevBuf<unsigned char> initCLAll;
-    DevBuf<unsigned char> nextKind;
-    DevBuf<int> flags, curSplatCount, adjacentReject, sampleIdx, numSamples, pushDim;
-    DevBuf<unsigned long long> counters, prof;
-    bool profileLean = false;  // LMC_PROF=1: the lean launch runs its region-timer instantiation (lmc_prof_read)
-    DevBuf<double> weightSum;
-    DevBuf<float> gradBuf;
-    // H2MC renders: hand-off state of the wave-cooperative pipeline (device/dh2coop.h)
-    DevBuf<float> h2Rec, h2Out, h2Gauss, h2Offset, h2Py, h2Px, h2PropContrib;
-    DevBuf<int> h2Step, h2Items, h2BinOf, h2Counts, h2SubList, h2SubCount;
-    H2Bins h2Bins[H2_MAX_PARTS][2] = {};  // [part][stage]
-    int h2Parts = 1, h2PartStride = 0;
-    const int *h2SplitOf = nullptr;  // the generic list h2SubList currently holds the two halves of (cut at the end of the step that built it, StepPhase2)
-    DevBuf<unsigned char> h2Kind;
-    H2Arrays H2{};
-    int h2HessGrid = 0, h2GaussGrid = 0;
-    // LMC renders with gradients: the cache-filling small steps as a pipeline (dh2coop.h MalaPipe; the buffers above, sized for it); LMC_MALA_PIPE=0: one launch
-    bool malaPipe = true;
-    MalaPipe MP{};
-    int gradStride = 0, stepGrid = 0;
-    // launch shape of the lean small-step kernel and the technique sort of its work list; LMC_LEAN_BLOCK / LMC_SORT_PLAIN
-    // override them for A/B runs (profiles/)
-    int leanBlock = 64, sortPlain = 0;  // (the lean launch runs one chain per thread: its launch function sizes the grid, step_small_plain.hip)
-    // chain relocation (device/relocate.hip): the chains kept physically grouped by technique from the first step on (fill phase included: the safety argument is at the launch site, StepPhase1); LMC_RELOCATE overrides
-    bool relocate = false;
-    DevBuf<int> chainId, slotOf, relocTileCount, relocTileHist, relocMembers, relocSorted, relocCount;
-    DevBuf<unsigned> relocPlacedKey;
-    DevBuf<unsigned char> stepKind;
-    bool relocFine = false;  // LMC_RELOC_FINE=1 (A/B, rejected: profiles/r06_r_*): the per-step relocation sorts its movers by the fine key (relocate.hip k_relf_*)
-    DevBuf<float> relocStaging;
-    RelocBuffers RB{};
-    long long relocations = 0;
-    int pendingResort = 0;
-    // the periodic full re-sort by (technique, screen Morton code) (relocate.hip): every resortEvery-th step ends with it; 0 = off
-    int resortEvery = 0, resortFirst = 0;
-    int resortEveryOpt = -1, resortFirstOpt = -1;  // lmc_set_option "resort_every" / "resort_first" (-1: not set)
-    long long stepsSinceInit = 0, resorts = 0;
-    DevBuf<unsigned> sortKeys[2];
-    DevBuf<int> sortVals[2], sortHist, sortScanSums;
-    RelocSortBuffers RS{};
-    // work lists (double buffered): [parity][large | smallGrad | smallPlain]
-    DevBuf<int> lists[2][3], listCounts[2];
-    int parity = 0;
-    // cache
-    CacheDimHost cacheDims[PSS_MAX_LENGTH + 1];
-    DCache cacheHost;
-    DevBuf<DCache> cacheDev;
-    DevBuf<int> cacheCounts;                 // rows filled per slot (dims 6, 8, 10, 12)
-    DevBuf<unsigned long long> pushTiles;    // scratch of the push launches: one word per 1024 chains
-    DevBuf<int> gridScratchStart, gridScratchCursor, gridScratchWordCount, gridTileSums;  // build-time scratch of the existence grids, sized for the largest dim's cell count (the builds are stream-ordered)
-    CachePushTargets pushT;                  // the cache rows themselves
-    CachePushTargets stageT;                 // ... and this rank's stage of a step's pushes (same row layout; kernels.hip k_push_apply)
-    PushStageLayout stageLayout;
-    DevBuf<float> pushStage, pushGather;     // the stage; the stages of all ranks after the exchange
-    DevBuf<int> warmCounts;                  // four zeros: the list lengths of the warm-up launches at the end of MLTInit
-    int *hostCounts = nullptr;               // pinned mirror of cacheCounts
-    hipEvent_t countsEvent = nullptr;        // ... is up to date (CacheApplyLaunch / CacheApplyFinish)
-    bool countsInFlight = false, appliedEarly = false;
-    // a gradient cache becoming ready (CacheApplyFinish): its rows come down, its existence grid is built and its kd-tree goes up on THIS stream, beside
-    // the step's launches; the device's copy of the cache struct is then refreshed from a pinned copy in stream order behind them
-    hipStream_t cacheStream = nullptr;
-    DCache *cachePinned = nullptr;
-    bool earlyApply = true;                  // LMC_EARLY_APPLY=0: a single rank also applies its pushes at the end of the step
-    int lastCounts[CACHE_SLOTS] = {0, 0, 0, 0}; // ... as last read back, and the steps run since (CacheApplyLaunch)
-    long long stepsSinceCounts = 0;
-    // the rows of a dim that is about to fill up, sent to the host behind the apply of the step that is expected to fill it (CacheApplyLaunch): when
-    // the counts say "ready" the rows are there already and the kd-tree build starts at once (the fetch was 0.2 ms of a 1.2 ms transition)
-    float *rowsPinned[CACHE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    bool rowsPrefetched[CACHE_SLOTS] = {false, false, false, false};
-    int lastDelta[CACHE_SLOTS] = {0, 0, 0, 0};  // rows added per step, as of the last two read-backs
-    // ... and the way up: a dim's kd-tree (nodes, then the point order) in a pinned buffer of its own, so that the copies are queued and the host goes on
-    // (pageable copies made the host wait for the stream, existence-grid builds included, once per dim: 0.3 ms)
-    char *treePinned[CACHE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t treesUpEvent = nullptr;
-    bool allCachesReady = false;
-    // the resident schedule (device/step_resident.h, RunResident): 0 = lock step only; K >= 1 = once the caches are frozen, up to K mutations
-    // of every chain per launch.  residentLanes: active chains per 64-lane wave ("resident_lanes"; 0 = ResidentLanes' choice); the rest is bookkeeping for
-    // lmc_resident_stats
-    int residentSteps = 0, residentLanes = 0;
-    long long residentLaunches = 0, lockSteps = 0;
-    double residentMs = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> residentEvents;  // one pair per resident launch not yet read by lmc_resident_stats
-    DevBuf<unsigned long long> residentGuard;                       // [chain-steps of resident launches, steps that would have needed a gradient / push]
-    bool residentResortPending = false;                             // a full re-sort is due before the next lock step (relocation on)
-    int mutationAtInit = -1;  // (mala, h2mc) the resident chain state was laid out for by lmc_chains_init; lmc_chains_step refuses any other
-    bool needGeneric = true;  // some chain may still need the generic small-step launch (gradient / deep cache tree)
-    bool genericTokenOnly = false;  // ... but only as the fallback of the lean launch without light sub-paths: a few blocks, no list sort
-    // init results
-    float normalization = 0.f;
-    std::vector<float> lengthFunc, lengthCdf;  // lengthDist of MLTInit (mlt.h:99), read by the multiplexed large step
-    float lengthFuncInt = 0.f;
-    long long numInitContribs = 0;
-    std::vector<unsigned char> initCL;            // MLTInit contributions in stream order (parity probe lmc_init_contribs)
-    std::vector<float> initLs;
-    std::vector<unsigned long long> initOffsets;  // first contribution of every init sample
-    // timing
-    struct StepEvents {
-        hipEvent_t e[8];  // main stream: step begin | lean launch begin | lean launch end | step end;  side streams: large begin / end, generic begin / end
-    };
-    // Events are recorded only between lmc_set_option("timing", 1) and the lmc_step_timing call that reads them, and come
-    // from a pool that is reused: a render that never asks for timings (dpt_amd) creates none.
-    bool timing = false;
-    std::vector<StepEvents> events, eventPool;
-    double smallMs = 0, largeMs = 0, largeOnlyMs = 0, genericMs = 0;  // accumulated by lmc_step_timing for lmc_kernel_timing / lmc_kernel_timing_split
-    ~lmc_ctx() {
-        for (lmc_ctx *peer : group)  // the other members of an in-process group hold raw pointers to this context
-            if (peer != this) {
-                peer->group.clear();
-                peer->world = 1, peer->rank = 0;
-            }
-        for (auto *v : {&events, &eventPool})
-            for (auto &ev : *v)
-                for (auto e : ev.e) (void)hipEventDestroy(e);
-        if (comm) {
-            try {
-                (void)GetRcclDestroy(comm);
-            } catch (...) {
-            }
-        }
-        if (hostCounts) (void)hipHostFree(hostCounts);
-        for (float *r : rowsPinned)
-            if (r) (void)hipHostFree(r);
-        for (char *r : treePinned)
-            if (r) (void)hipHostFree(r);
-        if (treesUpEvent) (void)hipEventDestroy(treesUpEvent);
-        if (cachePinned) (void)hipHostFree(cachePinned);
-        for (auto e : h2HeadDone)
-            if (e) (void)hipEventDestroy(e);
-        if (cacheStream) (void)hipStreamDestroy(cacheStream);
-        if (countsEvent) (void)hipEventDestroy(countsEvent);
-        for (auto st : partStream)
-            if (st) (void)hipStreamDestroy(st);
-        for (auto e : {partFork, partJoin[0], partJoin[1], partJoin[2], forkEvent, joinEvent[0], joinEvent[1], packedEvent, copiedEvent, filmReadyEvent, sliceReducedEvent, weightsCopiedEvent})
-            if (e) (void)hipEventDestroy(e);
-        for (auto st : sideStream)
-            if (st) (void)hipStreamDestroy(st);
-        for (auto &e : residentEvents) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
 
 // ------------------------------------------------------------------------------------------------ scene upload
 static void UploadScene(lmc_ctx *c) {
@@ -519,7 +228,7 @@ static void SyncOptions(lmc_ctx *c) {
     d.leanLightless = (lightlessMode == 2 || (lightlessMode == 1 && c->S.numLights == 1 && c->S.envLight >= 0)) ? 1 : 0;
 }
 
-static void UploadCacheStruct(lmc_ctx *c, hipStream_t after = nullptr) {
+void lmc_host::UploadCacheStruct(lmc_ctx *c, hipStream_t after) {
     if (c->cacheDev.n != 1) c->cacheDev.Alloc(1);
     if (after) {
         // in stream order behind what `after` holds (the step's launches, which read the struct as it was), from a pinned copy: the host goes on
@@ -536,19 +245,12 @@ static void UploadCacheStruct(lmc_ctx *c, hipStream_t after = nullptr) {
 }
 
 // ------------------------------------------------------------------------------------------------ ABI
+// (`extern "C"` is opened around the ABI functions only; everything internal has C++ linkage: file-local, or in lmc_host where context.h declares it)
 void LmcSetLastError(const std::string &what) { g_err = what; }  // last_error.h
 
 extern "C" {
 
 const char *lmc_last_error(void) { return g_err.c_str(); }
-
-#define LMC_TRY try {
-#define LMC_CATCH(ret)                \
-    }                                 \
-    catch (const std::exception &e) { \
-        g_err = e.what();             \
-        return ret;                   \
-    }
 
 lmc_ctx *lmc_create(const lmc_scene_desc *desc) {
     LMC_TRY
@@ -759,9 +461,10 @@ int lmc_image_write_exr(const char *path, const float *rgb, int w, int h) {
     LMC_CATCH(-1)
 }
 
+}  // extern "C"
+
 // ---- multi-GPU: the one data-path collective of the LMC path is a sum of the per-GPU films.  RCCL is
 // bound at run time (dlopen) so that single-GPU users and the CPU-side tests do not need it.
-extern "C++" {
 namespace {
 // Signatures, ncclUniqueId and the enum values come from rccl.h at BUILD time (decltype of the declarations: a mismatch with the
 // installed header is a compile error, not a silent ABI bug); the library itself is still bound at run time.
@@ -811,9 +514,8 @@ void RcclCheck(ncclResult_t rc, const char *what) {
     }
 }
 }  // namespace
-}  // extern "C++"
 
-static int GetRcclDestroy(void *comm) { return GetRccl().CommDestroy ? (int)GetRccl().CommDestroy((ncclComm_t)comm) : 0; }
+int lmc_host::GetRcclDestroy(void *comm) { return GetRccl().CommDestroy ? (int)GetRccl().CommDestroy((ncclComm_t)comm) : 0; }
 
 // ================================================================================================ MLTInit + chain set-up
 // MLTInit (mlt.h:41-154), sharded over the ranks of a job BY INIT STREAM (rank r runs the streams [V r / R, V (r + 1) / R): pass 1,
@@ -829,7 +531,6 @@ static int GetRcclDestroy(void *comm) { return GetRccl().CommDestroy ? (int)GetR
 // communicator (lmc_comm_init), device copies between the member contexts of an in-process group (lmc_group_*), nothing at all for a
 // single rank.  Init work and the 1.3 KB per chain of init state no longer grow with the number of ranks; what does is 5 bytes per
 // init contribution + 25 bytes per chain of the whole job on the host of every rank.
-extern "C++" {
 namespace {
 struct InitJob {
     // job
@@ -1070,17 +771,7 @@ void InitPhase3(lmc_ctx *c, InitJob &J) {
 }
 
 void InitPhase4(lmc_ctx *c, InitJob &J);
-// what the chains of a context are set up from, after MLTInit or from a checkpoint: the job's shape and the job-wide (technique, lsScore) tables
-struct ChainSetUp {
-    int numChainsTotal = 0, chainBegin = 0, chainEnd = 0;
-    long long perChain = 0, chainsNeedExtra = 0;
-    const std::vector<float> *seedLs = nullptr;
-    const std::vector<unsigned char> *seedCL = nullptr;
-    bool fromCheckpoint = false;  // the init states and the chains' words come from records (checkpoint.hip) instead of the init-state regeneration
-};
-void SetUpChains(lmc_ctx *c, const ChainSetUp &U);
 }  // namespace
-}  // extern "C++"
 
 // what the resident chain state is laid out for: mala, h2mc, samplecache (chain.path copies, cache rows with paths)
 static int MutationKey(const lmc_ctx *c) {
@@ -1090,7 +781,6 @@ static int MutationKey(const lmc_ctx *c) {
     return (o.mala ? 1 : 0) | (o.h2mc ? 2 : 0) | ((o.sampleFromGlobalCache && o.mala) ? 4 : 0) | (o.useLightCoordinateSampling ? 8 : 0);
 }
 static void WarmStepLaunches(lmc_ctx *c);
-extern "C++" {
 namespace {
 void InitPhase4(lmc_ctx *c, InitJob &J) {
     HIP_CHECK(hipSetDevice(c->device));
@@ -1129,9 +819,10 @@ void InitPhase4(lmc_ctx *c, InitJob &J) {
     U.seedLs = &J.seedLs, U.seedCL = &J.seedCL;
     SetUpChains(c, U);
 }
+}  // namespace
 // the chain arrays and everything the step loop needs beside them, allocated and in the state of a fresh population: identity layout (slot = chain),
 // empty caches, zeroed film and counters, every chain queued for a large step.  After a checkpoint's records are in, lmc_checkpoint_load rebuilds the lists.
-void SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
+void lmc_host::SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int numChainsTotal = U.numChainsTotal, chainBegin = U.chainBegin, chainEnd = U.chainEnd;
@@ -1361,7 +1052,7 @@ void SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     c->chainsSince = std::chrono::steady_clock::now();
 }
 
-
+namespace {
 // the ranks of one job run the four phases in lock step; `g` = the member contexts this process drives (one for an RCCL rank)
 void RunInit(const std::vector<lmc_ctx *> &g, long long numInitSamples, int numChainsTotal, int initThreads, const std::vector<std::pair<int, int>> &ranges,
              long long perChain, long long chainsNeedExtra) {
@@ -1396,12 +1087,11 @@ void RunInit(const std::vector<lmc_ctx *> &g, long long numInitSamples, int numC
     for (size_t k = 0; k < g.size(); k++) InitPhase4(g[k], *jobs[k]);
 }
 }  // namespace
-}  // extern "C++"
 
 // What the film merge of an in-process group needs, set up ONCE when the group is: direct peer access between the members' devices (checked
 // with hipDeviceCanAccessPeer, enabled once per ordered pair; without it the runtime stages every peer copy through the host), every member's
 // staging for the slices it pulls, the events the merge is ordered by.  Nothing is allocated inside lmc_group_film_reduce.
-static void GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
+void lmc_host::GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
     const size_t n = g.size();
     std::vector<int> devs;
     for (lmc_ctx *c : g)
@@ -1433,6 +1123,8 @@ static void GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
             if (!*e) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
 }
+
+extern "C" {
 
 int lmc_chains_init(lmc_ctx *c, long long numInitSamples, int numChainsTotal, int initThreads, int chainBegin, int chainEnd, long long perChain,
                     long long chainsNeedExtra) {
@@ -1482,54 +1174,6 @@ int lmc_group_info(lmc_ctx **ctxs, int n, long long *out4) {
     LMC_CATCH(-1)
 }
 
-// ---- CPU test hooks (no GPU): the host-side plan of the sharded MLTInit (shardplan.h), from the very blocks the ranks exchange
-int lmc_shard_layout(int world, int rank, int initThreads, long long numInitSamples, long long *out5) {
-    LMC_TRY
-    if (world < 1 || rank < 0 || rank >= world || initThreads < 1) throw std::runtime_error("lmc_shard_layout: bad arguments");
-    const lmc::ShardLayout L = lmc::MakeShardLayout(world, rank, initThreads, numInitSamples);
-    out5[0] = L.t0, out5[1] = L.t1, out5[2] = L.g0, out5[3] = L.g1, out5[4] = L.maxLocalSamples;
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_shard_counts_probe(int world, int initThreads, long long numInitSamples, const unsigned char *paddedCounts, long long maxLocalSamples,
-                           unsigned long long *rankFirst) {
-    LMC_TRY
-    std::vector<unsigned long long> hOff, rf;
-    lmc::AssembleCounts(world, initThreads, numInitSamples, paddedCounts, maxLocalSamples, hOff, rf);
-    for (int r = 0; r <= world; r++) rankFirst[r] = rf[r];
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_shard_plan_probe(int world, int initThreads, long long numInitSamples, int numChainsTotal, const unsigned char *paddedCounts, long long maxLocalSamples,
-                         const unsigned char *paddedCL, const float *paddedLs, long long maxLocalContribs, long long *seedSample, unsigned char *seedCL,
-                         float *seedLs, int *ownedBegin, float *normalization) {
-    LMC_TRY
-    std::vector<unsigned long long> hOff, rf;
-    lmc::AssembleCounts(world, initThreads, numInitSamples, paddedCounts, maxLocalSamples, hOff, rf);
-    const unsigned long long total = rf[world];
-    if ((long long)total < numChainsTotal) throw std::runtime_error("MLT initialization failed, consider using a larger number of initial samples or smaller number of chains");
-    std::vector<unsigned char> cl(total);
-    std::vector<float> ls(total);
-    lmc::AssembleBlocks(world, rf, paddedCL, (unsigned long long)maxLocalContribs, 1, cl.data());
-    lmc::AssembleBlocks(world, rf, paddedLs, (unsigned long long)maxLocalContribs, sizeof(float), ls.data());
-    std::vector<uint32_t> hostTab(64);
-    Rng hr;
-    hr.tab = hostTab.data();
-    hr.state = PcgSeed((uint64_t)total, hr.tab);
-    hr.ticks = 0;
-    std::vector<long long> ss;
-    std::vector<unsigned char> sc;
-    std::vector<float> sl;
-    float norm = 0.f;
-    lmc::SeedWalk(numInitSamples, numChainsTotal, hOff, cl.data(), ls.data(), [](void *r) { return ((Rng *)r)->Uniform(); }, &hr, ss, sc, sl, norm);
-    const std::vector<int> ob = lmc::OwnedRanges(world, initThreads, numInitSamples, ss);
-    for (int i = 0; i < numChainsTotal; i++) seedSample[i] = ss[i], seedCL[i] = sc[i], seedLs[i] = sl[i];
-    for (int r = 0; r <= world; r++) ownedBegin[r] = ob[r];
-    *normalization = norm;
-    return 0;
-    LMC_CATCH(-1)
-}
-
 long long lmc_init_contribs(lmc_ctx *c, long long cap, long long *sample, int *cl, float *ls) {
     const long long n = (long long)c->initCL.size();
     size_t g = 0;
@@ -1545,6 +1189,8 @@ int lmc_init_result(lmc_ctx *c, float *normalization, long long *numContribs) {
     if (numContribs) *numContribs = c->numInitContribs;
     return 0;
 }
+
+}  // extern "C"
 
 // After every step, until all caches in use are full: apply the step's pushes (three small launches for all dims), read the
 // four fill counts back and build the kd-tree of a dim that has just reached PSS_MAX_SIZE (global_cache.h:85-92), so
@@ -1564,7 +1210,7 @@ static unsigned LeanDims(const lmc_ctx *c) {
 //   CacheApplyFinish  the kd-tree and the existence grid of a dim that has just reached PSS_MAX_SIZE built (global_cache.h:85-92), so that
 //                     the next step already queries it -- the lock-step contract the oracle implements too
 // Every rank applies the same rows to the same cache, so "which dims are ready" is the same on all of them without asking.
-static bool CachePending(lmc_ctx *c) {
+bool lmc_host::CachePending(lmc_ctx *c) {
     bool anyPending = false;
     for (int d = 6; d <= PSS_MAX_LENGTH; d += 2) anyPending = anyPending || (c->cacheDims[d].relevant && !c->cacheDims[d].ready);
     if (!anyPending) {
@@ -1616,7 +1262,7 @@ static void CacheApplyLaunch(lmc_ctx *c, hipStream_t s) {
 }
 // A dim whose rows, existence grid and kd-tree are in place (or on their way, in stream order) enters the host's copy of the cache struct: what
 // CacheApplyFinish does when a dim fills up, and lmc_checkpoint_load for the dims its file holds ready
-static void PublishCacheDim(lmc_ctx *c, int d, const lmc::KdTreeResult &t, hipStream_t s) {
+void lmc_host::PublishCacheDim(lmc_ctx *c, int d, const lmc::KdTreeResult &t, hipStream_t s) {
     CacheDimHost &cd = c->cacheDims[d];
     DCacheDim &D = c->cacheHost.d[d];
     D.gridWords = c->useOccFilter ? cd.gridWords.p : nullptr, D.gridCellStart = cd.gridCellStart.p, D.gridIdx = cd.gridIdx.p, D.gridG = cd.gridG, D.gridM = cd.gridM;
@@ -1763,7 +1409,6 @@ static void CacheApplyFinish(lmc_ctx *c) {
     if (numReady) mark("cache struct refreshed");  // beside: the step's launches are still running and read the struct as it was; `s` is behind all of them (StepPhase1's joins)
 }
 
-extern "C++" {
 namespace {
 void CheckSteppable(lmc_ctx *c) {
     if (c->N <= 0) throw std::runtime_error("lmc_chains_step before lmc_chains_init");
@@ -1773,7 +1418,8 @@ void CheckSteppable(lmc_ctx *c) {
     if (c->S.opt.sampleCache && !c->scene->options.largeStepMultiplexed)
         throw std::runtime_error("samplecache needs largestepmultiplexed (mutation_large_cache.h:33)");
 }
-StepParams MakeStepParams(const lmc_ctx *c) {
+}  // namespace
+StepParams lmc_host::MakeStepParams(const lmc_ctx *c) {
     StepParams P;
     P.normalization = c->normalization, P.numChains = c->numChainsTotal, P.chainBegin = c->chainBegin, P.useGradient = c->useGradient, P.maxDervDepth = c->maxDervDepth, P.expFlags = c->expFlags;
     const bool mux = c->scene->options.largeStepMultiplexed;
@@ -1782,6 +1428,7 @@ StepParams MakeStepParams(const lmc_ctx *c) {
     for (int k = 0; k <= P.lengthCount; k++) P.lengthCdf[k] = c->lengthCdf[k];
     return P;
 }
+namespace {
 // which large-step / generic small-step kernel the options in force select (cnt: the three list lengths on the device)
 Film StepFilm(lmc_ctx *c) { return c->filmExact ? FilmFx(c->filmFx.p, c->S.cam.width, c->S.cam.height) : Film{c->film.p, c->S.cam.width, c->S.cam.height}; }
 void LaunchLarge(lmc_ctx *c, const Film &film, const StepParams &P, int cur, const int *cnt, const NextLists &next, hipStream_t sL) {
@@ -1997,7 +1644,6 @@ void DebugResort(lmc_ctx *c) {
 // second half: the gathered pushes applied (a cache that becomes ready at the end of this step -- mlt.cpp: push() flips is_ready
 // inside the step -- is seen by the list build: chains whose next step no longer needs a gradient go to the lean launch right
 // away), then the work lists of the next step
-void BuildNextLists(lmc_ctx *c, int nxt);
 void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -2030,8 +1676,9 @@ void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
         c->events.push_back(ev);
     }
 }
+}  // namespace
 // the work lists of the step that runs next, into lists[nxt] (their counts zeroed by the caller), on the step stream
-void BuildNextLists(lmc_ctx *c, int nxt) {
+void lmc_host::BuildNextLists(lmc_ctx *c, int nxt) {
     hipStream_t s = c->stream;
     NextLists next{c->lists[nxt][0].p, c->lists[nxt][1].p, c->lists[nxt][2].p, c->listCounts[nxt].p};
     const int sortPlain = c->relocate ? 0 : c->sortPlain;  // relocated chains are grouped already, and in place
@@ -2051,8 +1698,6 @@ void BuildNextLists(lmc_ctx *c, int nxt) {
         c->h2SplitOf = c->lists[nxt][1].p;
     }
 }
-}  // namespace
-}  // extern "C++"
 // The first launch of a kernel on a stream pays one-time runtime work (code object upload, the private-memory ring of the queue:
 // between 4 ms and, on a cold box, 140 ms for the lean kernel at 2^20 chains, profiles/r03_o_step_timeline.jsonl step 0).  MLTInit
 // ends by launching the step kernels of the options in force once with EMPTY work lists, so that this is paid at set-up and not
@@ -2077,7 +1722,6 @@ static void WarmStepLaunches(lmc_ctx *c) {
     HIP_CHECK(hipStreamSynchronize(sG));
     HIP_CHECK(hipStreamSynchronize(s));
 }
-extern "C++" {
 namespace {
 // ---- the resident schedule (lmc_set_option "resident_steps" = K; device/step_resident.h)
 // Cap of K: one resident launch runs at most kResidentBudget chain-steps and at most kResidentMaxK steps per chain, so that it stays in the tens of
@@ -2089,11 +1733,13 @@ namespace {
 constexpr long long kResidentBudget = 1ll << 21;
 constexpr int kResidentMaxK = 32;
 int ResidentLanes(const lmc_ctx *c) { return c->residentLanes ? c->residentLanes : c->N <= 65536 ? 32 : 64; }
-int ResidentK(const lmc_ctx *c) {
+}  // namespace
+int lmc_host::ResidentK(const lmc_ctx *c) {
     if (c->residentSteps <= 0 || c->N <= 0) return 0;
     const long long byBudget = std::max(1ll, kResidentBudget / (long long)c->N);
     return (int)std::min<long long>({(long long)c->residentSteps, (long long)kResidentMaxK, byBudget});
 }
+namespace {
 // May this member's remaining steps run resident?  Not while a relevant cache dim is filling: the lock-step contract orders the pushes by step
 // (mlt.cpp:120-127).  CachePending is what StepPhase1 would ask at the head of this very step (it sets allCachesReady from the step in which the
 // last cache became ready); plain MLT never fills a cache, so its chains run resident from the first step.
@@ -2219,7 +1865,8 @@ void RunSteps(const std::vector<lmc_ctx *> &g, int nSteps) {
     }
 }
 }  // namespace
-}  // extern "C++"
+
+extern "C" {
 
 int lmc_chains_step(lmc_ctx *c, int nSteps) {
     LMC_TRY
@@ -2418,345 +2065,6 @@ int lmc_film_overflow(lmc_ctx *c, long long *n) {
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(n, c->filmFx.p + c->film.n, sizeof(long long), hipMemcpyDeviceToHost));
     return 0;
-    LMC_CATCH(-1)
-}
-
-// DirectLighting(scene, directBuffer), direct.cpp:4-54 (skipped when mindepth > 2 or maxdepth < 1, :6-8)
-static int PathTracePass(lmc_ctx *c, int spp, int minDepth, int maxDepth);
-int lmc_direct_lighting(lmc_ctx *c, int directSpp) {
-    if (c->S.opt.minDepth > 2 || c->S.opt.maxDepth < 1) directSpp = 0;
-    return PathTracePass(c, directSpp, std::min(c->S.opt.minDepth, 2), std::min(c->S.opt.maxDepth, 2));
-}
-// GeneratePath with the scene's own depth range: the reference's "mc" integrator kernel (pathtrace.cpp uses the same
-// generator); here a cross-check of the MLT result, not a product path
-int lmc_path_trace(lmc_ctx *c, int spp) { return PathTracePass(c, spp, c->S.opt.minDepth, c->S.opt.maxDepth); }
-// plain Monte Carlo over GeneratePathBidir samples (paths of length >= 3), `spp` samples per pixel on average; result
-// (already scaled to radiance) through lmc_direct_read.  Cross-check estimator for tests / DESIGN.md, not a product path.
-int lmc_bidir_mc(lmc_ctx *c, int spp) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    const int W = c->S.cam.width, H = c->S.cam.height;
-    c->directFilm.Alloc((size_t)W * H * 3);
-    const int nThreads = 65536;
-    const long long total = (long long)spp * W * H;
-    const int per = (int)((total + nThreads - 1) / nThreads);
-    DevBuf<uint32_t> tab;
-    DevBuf<float> contrib;
-    tab.Alloc((size_t)nThreads * 64, false), contrib.Alloc((size_t)nThreads * MAXCONTRIB * CONTRIB_WORDS, false);
-    Film film{c->directFilm.p, W, H};
-    LaunchBidirMC(c->S, film, nThreads, per, tab.p, contrib.p, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    std::vector<float> h = c->directFilm.Download();
-    const float scale = (float)((double)W * H / ((double)per * nThreads));
-    for (auto &v : h) v *= scale;
-    HIP_CHECK(hipMemcpy(c->directFilm.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-    LMC_CATCH(-1)
-}
-static int PathTracePass(lmc_ctx *c, int directSpp, int minDepth, int maxDepth) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    const int W = c->S.cam.width, H = c->S.cam.height;
-    c->directFilm.Alloc((size_t)W * H * 3);
-    if (directSpp <= 0) return 0;
-    const int nTiles = ((W + 15) / 16) * ((H + 15) / 16);
-    DevBuf<uint32_t> tab;
-    tab.Alloc((size_t)nTiles * 64, false);
-    Film film{c->directFilm.p, W, H};
-    const char *e = getenv("LMC_DIRECT_WAVE");  // =0: the one-thread-per-tile kernel (A/B, and the checker of the wave kernel)
-    LaunchDirect(c->S, film, directSpp, minDepth, maxDepth, c->bvhDepth, !e || atoi(e) != 0, tab.p, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipGetLastError());
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// The mc integrator (PathTrace, pathtrace.cpp:14-78; device/mc.hip): stream ids [begin, end) of nTiles * spp into the MC film.
-// Generator, depth range and seed offset are the scene's (<dpt bidirectional / mindepth / maxdepth / seedoffset>).
-// Float mode: the film is cleared and every contribution added as contrib / spp.  Exact mode ("mc_film_exact", INTEGRATION.md "Exact mc film"): the film is
-// the integer sum of the unweighted contributions, knows which stream ids it holds (host/mcfilm.h McCoverage) and is divided by spp when it is read, so
-// calls can add to it (lmc_mc_accumulate), members' films can be summed in any order (lmc_group_mc_render) and a file can carry it (lmc_mc_save / _load).
-// Either mode runs a call as launches of at most "mc_launch_streams" stream ids on the context's stream.
-extern "C++" {
-namespace {
-uint64_t HashSceneFiles(const lmc::Scene &sc);  // (the checkpoint section below)
-
-long long McTiles(const lmc_ctx *c) { return (long long)((c->S.cam.width + 15) / 16) * ((c->S.cam.height + 15) / 16); }
-size_t McWords(const lmc_ctx *c) { return (size_t)c->S.cam.width * c->S.cam.height * 3; }
-
-void McCheckRange(const char *what, lmc_ctx *c, int spp, long long &begin, long long &end) {
-    if (spp < 1) throw std::runtime_error(std::string(what) + ": spp >= 1 expected");
-    const long long total = McTiles(c) * spp;
-    if (end == -1) end = total;
-    if (begin < 0 || begin > end || end > total)
-        throw std::runtime_error(std::string(what) + ": stream range [" + std::to_string(begin) + ", " + std::to_string(end) + ") outside [0, " + std::to_string(total) + ")");
-}
-
-// the launches of one call: [begin, end) in chunks (mcfilm.h McChunks), one table scratch sized for the largest of them, one wait at the end
-void McRunLaunches(lmc_ctx *c, const Film &film, int spp, long long begin, long long end) {
-    const std::vector<lmc::McRange> chunks = lmc::McChunks(begin, end, McTiles(c), c->mcLaunchStreams);
-    long long maxThreads = 0;
-    for (const lmc::McRange &r : chunks) maxThreads = std::max(maxThreads, MCThreads(c->S, r.first, r.second));
-    DevBuf<uint32_t> tab;  // written only by a stream that ticks (once per 2^32 draws)
-    tab.Alloc((size_t)((maxThreads + 63) / 64 * 64) * 64, false);
-    for (const lmc::McRange &r : chunks)
-        LaunchMC(c->S, film, c->scene->options.bidirectional, spp, c->S.opt.minDepth, c->S.opt.maxDepth, r.first, r.second, tab.p, c->mcCounters.p, c->stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->mcLaunches = (int)chunks.size();
-}
-
-// an empty exact film: words, overflow word, counters and coverage cleared
-void McStartExact(lmc_ctx *c) {
-    if (c->mcFilmFx.n != McWords(c) + 1) c->mcFilmFx.Alloc(McWords(c) + 1, false);
-    if (c->mcCounters.n != 2) c->mcCounters.Alloc(2, false);
-    HIP_CHECK(hipMemsetAsync(c->mcFilmFx.p, 0, c->mcFilmFx.n * sizeof(long long), c->stream));
-    HIP_CHECK(hipMemsetAsync(c->mcCounters.p, 0, 2 * sizeof(unsigned long long), c->stream));
-    c->mcCoverage.Clear();
-    c->mcFilmIsExact = true;
-    c->mcDivisor = 0;
-}
-
-// adds [begin, end) to the exact film the context holds; refused, the film untouched, if the range would count a sample twice
-void McAccumulate(const char *what, lmc_ctx *c, int spp, long long begin, long long end) {
-    const long long total = McTiles(c) * spp;
-    if (c->mcCoverage.End() > total)
-        throw std::runtime_error(std::string(what) + ": the film holds stream ids up to " + std::to_string(c->mcCoverage.End()) + ", beyond the " + std::to_string(total) +
-                                 " of " + std::to_string(spp) + " spp");
-    if (c->mcCoverage.Overlaps(begin, end))
-        throw std::runtime_error(std::string(what) + ": stream range [" + std::to_string(begin) + ", " + std::to_string(end) +
-                                 ") overlaps what the film already holds (its samples would be counted twice); the film is unchanged");
-    McRunLaunches(c, FilmFx(c->mcFilmFx.p, c->S.cam.width, c->S.cam.height), spp, begin, end);
-    c->mcCoverage.Add(begin, end);
-    c->mcDivisor = spp;
-}
-
-lmc::McFileHeader McHeaderOf(lmc_ctx *c) {
-    lmc::McFileHeader H;
-    if (!c->sceneHash) c->sceneHash = HashSceneFiles(*c->scene);
-    const lmc::DptOptions &o = c->scene->options;
-    H.sceneHash = c->sceneHash;
-    H.forceDiffuse = c->forceDiffuse, H.width = c->S.cam.width, H.height = c->S.cam.height, H.minDepth = o.minDepth, H.maxDepth = o.maxDepth, H.seedOffset = o.seedOffset;
-    H.bidirectional = o.bidirectional ? 1 : 0;
-    H.nTiles = McTiles(c);
-    return H;
-}
-}  // namespace
-}
-
-int lmc_mc_render(lmc_ctx *c, int spp, long long streamBegin, long long streamEnd) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    McCheckRange("lmc_mc_render", c, spp, streamBegin, streamEnd);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->mcExactOpt) {
-        McStartExact(c);
-        McAccumulate("lmc_mc_render", c, spp, streamBegin, streamEnd);
-        return 0;
-    }
-    const int W = c->S.cam.width, H = c->S.cam.height;
-    c->mcFilmIsExact = false;
-    c->mcCoverage.Clear();
-    if (c->mcFilm.n != (size_t)W * H * 3) c->mcFilm.Alloc((size_t)W * H * 3, false);
-    if (c->mcCounters.n != 2) c->mcCounters.Alloc(2, false);
-    HIP_CHECK(hipMemsetAsync(c->mcFilm.p, 0, c->mcFilm.n * sizeof(float), c->stream));
-    HIP_CHECK(hipMemsetAsync(c->mcCounters.p, 0, 2 * sizeof(unsigned long long), c->stream));
-    McRunLaunches(c, Film{c->mcFilm.p, W, H}, spp, streamBegin, streamEnd);
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_accumulate(lmc_ctx *c, int spp, long long streamBegin, long long streamEnd) {
-    LMC_TRY
-    if (!c->mcExactOpt) throw std::runtime_error("lmc_mc_accumulate: the mc film is in float mode; only the exact film (lmc_set_option \"mc_film_exact\" = 1) can be added to");
-    HIP_CHECK(hipSetDevice(c->device));
-    McCheckRange("lmc_mc_accumulate", c, spp, streamBegin, streamEnd);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (!c->mcFilmIsExact) McStartExact(c);  // no exact film yet: an empty one
-    McAccumulate("lmc_mc_accumulate", c, spp, streamBegin, streamEnd);
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_coverage(lmc_ctx *c, long long *ranges, int cap) {
-    LMC_TRY
-    if (!c->mcFilmIsExact) return 0;
-    const std::vector<lmc::McRange> &r = c->mcCoverage.ranges;
-    for (int k = 0; k < (int)r.size() && k < cap; k++) ranges[2 * k] = r[k].first, ranges[2 * k + 1] = r[k].second;
-    return (int)r.size();
-    LMC_CATCH(-1)
-}
-int lmc_mc_read(lmc_ctx *c, float *rgb) {
-    LMC_TRY
-    if (c->mcFilmIsExact ? c->mcFilmFx.n == 0 || c->mcDivisor < 1 : c->mcFilm.n == 0) throw std::runtime_error("lmc_mc_read before lmc_mc_render");
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->mcFilmIsExact) {  // converted on the device, float(double(q) * 2^-32 / double(spp))
-        if (c->mcFilm.n != McWords(c)) c->mcFilm.Alloc(McWords(c), false);
-        LaunchMCFixedToFloat(c->mcFilmFx.p, c->mcFilm.p, c->mcFilm.n, c->mcDivisor, c->stream);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-    }
-    HIP_CHECK(hipMemcpy(rgb, c->mcFilm.p, c->mcFilm.n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_read_fixed(lmc_ctx *c, long long *words) {
-    LMC_TRY
-    if (!c->mcFilmIsExact || c->mcFilmFx.n == 0) throw std::runtime_error("lmc_mc_read_fixed: the mc film is in float mode (lmc_set_option \"mc_film_exact\" = 1 before lmc_mc_render)");
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(words, c->mcFilmFx.p, McWords(c) * sizeof(long long), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_overflow(lmc_ctx *c, long long *n) {
-    LMC_TRY
-    *n = 0;
-    if (!c->mcFilmIsExact || c->mcFilmFx.n == 0) return 0;
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(n, c->mcFilmFx.p + McWords(c), sizeof(long long), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_stats(lmc_ctx *c, long long *out2) {
-    LMC_TRY
-    out2[0] = out2[1] = 0;
-    if (c->mcCounters.n != 2) return 0;
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    const std::vector<unsigned long long> v = c->mcCounters.Download();
-    out2[0] = (long long)v[0], out2[1] = (long long)v[1];
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// [begin, end) split at begin + (end - begin) * k / n, the shards rendered concurrently (one host thread per member), then member 0's film += member k's for
-// k = 1 .. n - 1 in that order on member 0's device: int64 words in exact mode, floats in float mode (the order a host loop over the members would add in)
-// lmc_group_mc_accumulate: the same, but member 0 adds its shard to the exact film it holds (the others render theirs into cleared films), so member 0
-// ends with what it held plus the whole range
-static int GroupMcRender(const char *what_, bool accumulate, lmc_ctx **ctxs, int n, int spp, long long streamBegin, long long streamEnd) {
-    LMC_TRY
-    const std::string what(what_);
-    if (n < 1 || !ctxs) throw std::runtime_error(what + ": empty group");
-    std::vector<lmc_ctx *> g(ctxs, ctxs + n);
-    for (int r = 0; r < n; r++) {
-        if (!g[r]) throw std::runtime_error(what + ": null member");
-        for (int q = 0; q < r; q++)
-            if (g[q] == g[r]) throw std::runtime_error(what + ": a context is listed twice (a device may be, through a context of its own)");
-        if (g[r]->mcExactOpt != g[0]->mcExactOpt)
-            throw std::runtime_error(what + ": the members differ in mc_film_exact (member 0: " + std::to_string((int)g[0]->mcExactOpt) + ", member " + std::to_string(r) + ": " +
-                                     std::to_string((int)g[r]->mcExactOpt) + "); a group's films are summed in one format");
-        if (g[r]->S.cam.width != g[0]->S.cam.width || g[r]->S.cam.height != g[0]->S.cam.height) throw std::runtime_error(what + ": the members differ in film size");
-    }
-    McCheckRange(what_, g[0], spp, streamBegin, streamEnd);
-    if (accumulate && !g[0]->mcExactOpt) throw std::runtime_error(what + ": the mc film is in float mode; only the exact film (lmc_set_option \"mc_film_exact\" = 1) can be added to");
-    if (accumulate && g[0]->mcFilmIsExact && g[0]->mcCoverage.Overlaps(streamBegin, streamEnd))
-        throw std::runtime_error(what + ": stream range [" + std::to_string(streamBegin) + ", " + std::to_string(streamEnd) +
-                                 ") overlaps what member 0's film already holds (its samples would be counted twice); the film is unchanged");
-    const long long len = streamEnd - streamBegin;
-    std::vector<int> rc(n, 0);
-    std::vector<std::string> err(n);  // the last error is per thread
-    std::vector<std::thread> th;
-    for (int k = 0; k < n; k++)
-        th.emplace_back([&, k] {
-            const long long b = streamBegin + len * k / n, e = streamBegin + len * (k + 1) / n;
-            rc[k] = accumulate && k == 0 ? lmc_mc_accumulate(g[k], spp, b, e) : lmc_mc_render(g[k], spp, b, e);
-            if (rc[k] != 0) err[k] = g_err;
-        });
-    for (std::thread &t : th) t.join();
-    for (int k = 0; k < n; k++)
-        if (rc[k] != 0) throw std::runtime_error(what + ": member " + std::to_string(k) + ": " + err[k]);
-    lmc_ctx *c = g[0];
-    const bool exact = c->mcFilmIsExact;
-    const size_t words = exact ? McWords(c) + 1 : McWords(c), bytes = words * (exact ? sizeof(long long) : sizeof(float));
-    if (n > 1) {
-        HIP_CHECK(hipSetDevice(c->device));
-        DevBuf<unsigned char> stage;
-        DevBuf<long long> counterStage;
-        stage.Alloc(bytes, false), counterStage.Alloc(2, false);
-        for (int k = 1; k < n; k++) {  // (every member's stream is idle: lmc_mc_render waits for its launches)
-            HIP_CHECK(hipMemcpyPeerAsync(stage.p, c->device, exact ? (const void *)g[k]->mcFilmFx.p : (const void *)g[k]->mcFilm.p, g[k]->device, bytes, c->stream));
-            HIP_CHECK(hipMemcpyPeerAsync(counterStage.p, c->device, g[k]->mcCounters.p, g[k]->device, 2 * sizeof(long long), c->stream));
-            if (exact) LaunchAddIntoI64(c->mcFilmFx.p, reinterpret_cast<const long long *>(stage.p), words, c->stream);
-            else
-                LaunchAddInto(c->mcFilm.p, reinterpret_cast<const float *>(stage.p), words, c->stream);
-            LaunchAddIntoI64(reinterpret_cast<long long *>(c->mcCounters.p), counterStage.p, 2, c->stream);
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (int k = 1; k < n; k++) {  // member 0 holds the whole; the others are left cleared
-            lmc_ctx *m = g[k];
-            if (exact)
-                for (const lmc::McRange &r : m->mcCoverage.ranges) c->mcCoverage.Add(r.first, r.second);
-            HIP_CHECK(hipSetDevice(m->device));
-            if (exact) HIP_CHECK(hipMemsetAsync(m->mcFilmFx.p, 0, m->mcFilmFx.n * sizeof(long long), m->stream));
-            else
-                HIP_CHECK(hipMemsetAsync(m->mcFilm.p, 0, m->mcFilm.n * sizeof(float), m->stream));
-            HIP_CHECK(hipMemsetAsync(m->mcCounters.p, 0, 2 * sizeof(unsigned long long), m->stream));
-            HIP_CHECK(hipStreamSynchronize(m->stream));
-            m->mcCoverage.Clear();
-        }
-        HIP_CHECK(hipSetDevice(c->device));
-    }
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_group_mc_render(lmc_ctx **ctxs, int n, int spp, long long streamBegin, long long streamEnd) {
-    return GroupMcRender("lmc_group_mc_render", false, ctxs, n, spp, streamBegin, streamEnd);
-}
-int lmc_group_mc_accumulate(lmc_ctx **ctxs, int n, int spp, long long streamBegin, long long streamEnd) {
-    return GroupMcRender("lmc_group_mc_accumulate", true, ctxs, n, spp, streamBegin, streamEnd);
-}
-
-// The exact mc film as a file (host/mcfilm.h has the layout): the fingerprint of what the film was rendered from, its divisor, counters and coverage, the words.
-int lmc_mc_save(lmc_ctx *c, const char *path) {
-    LMC_TRY
-    if (!path) throw std::runtime_error("lmc_mc_save: no path");
-    if (!c->mcFilmIsExact || c->mcFilmFx.n == 0) throw std::runtime_error("lmc_mc_save: the context holds no exact mc film (lmc_set_option \"mc_film_exact\" = 1 before lmc_mc_render)");
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    lmc::McFileHeader H = McHeaderOf(c);
-    const std::vector<long long> words = c->mcFilmFx.Download();
-    const std::vector<unsigned long long> counters = c->mcCounters.Download();
-    H.spp = c->mcDivisor, H.paths = (int64_t)counters[0], H.contributions = (int64_t)counters[1], H.overflow = words[McWords(c)];
-    H.coverage = c->mcCoverage;
-    lmc::McFileWrite(path, H, words.data());
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_mc_load(lmc_ctx *c, const char *path) {
-    LMC_TRY
-    if (!path) throw std::runtime_error("lmc_mc_load: no path");
-    if (!c->mcExactOpt) throw std::runtime_error("lmc_mc_load: the mc film is in float mode; a state file holds an exact film (lmc_set_option \"mc_film_exact\" = 1)");
-    std::vector<long long> words;
-    const lmc::McFileHeader F = lmc::McFileRead(path, &words);
-    if (const char *field = lmc::McFileMismatch(F, McHeaderOf(c)))
-        throw std::runtime_error(std::string("lmc_mc_load: ") + path + " was written for another render: it differs in " + field);
-    if (F.spp < 1 || F.spp > 0x7fffffff || F.coverage.End() > F.nTiles * F.spp) throw std::runtime_error(std::string("lmc_mc_load: ") + path + " has an inconsistent header (spp / coverage)");
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    words.push_back(F.overflow);
-    const unsigned long long counters[2] = {(unsigned long long)F.paths, (unsigned long long)F.contributions};
-    McStartExact(c);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(c->mcFilmFx.p, words.data(), words.size() * sizeof(long long), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(c->mcCounters.p, counters, sizeof(counters), hipMemcpyHostToDevice));
-    c->mcCoverage = F.coverage;
-    c->mcDivisor = (int)F.spp;
-    return 0;
-    LMC_CATCH(-1)
-}
-// host only: the header of a state file as one JSON document (lmc_scene_dump's convention: at most cap - 1 characters + NUL, returns the full length, -1 on error)
-long long lmc_mc_file_info(const char *path, char *out, long long cap) {
-    LMC_TRY
-    if (!path) throw std::runtime_error("lmc_mc_file_info: no path");
-    const std::string j = lmc::McFileJson(lmc::McFileRead(path, nullptr));
-    if (out && cap > 0) {
-        const size_t n = std::min<size_t>(j.size(), (size_t)cap - 1);
-        memcpy(out, j.data(), n);
-        out[n] = 0;
-    }
-    return (long long)j.size();
     LMC_CATCH(-1)
 }
 
@@ -2979,1202 +2287,5 @@ int lmc_chain_summary(lmc_ctx *c, int which, float *out, int stride) {
     return (int)N;
     LMC_CATCH(-1)
 }
-
-// ------------------------------------------------------------------------------------------------ checkpoint and resume
-// One little-endian file (INTEGRATION.md "Checkpoint and resume"): header (magic, version, the fingerprint of what the states depend on, the job's
-// shape, steps and seconds so far) | job-wide state, once (init results, the gradient caches' rows, counters, film) | one fixed-size record per
-// chain of the JOB, in chain order (device/checkpoint.hip).  Nothing in it depends on the slots the chains lived in, on the schedule that ran
-// them or on how many members of an in-process group held them, so it loads into one context or into a group of any size.
-extern "C++" {
-namespace {
-constexpr char kCkptMagic[8] = {'L', 'M', 'C', 'C', 'K', 'P', 'T', '\n'};
-// version 1: the film section is W*H*3 floats (byte for byte what every earlier build wrote); version 2: the header's filmFormat is 1 and the film
-// section is W*H*3 signed 64-bit fixed-point words (exact mode, INTEGRATION.md "Exact film").  Float-mode renders keep writing version 1.
-constexpr uint32_t kCkptVersion = 1, kCkptVersionExact = 2;
-constexpr int32_t kFilmFloat32 = 0, kFilmFixed64 = 1;
-const char *FilmFormatName(int32_t f) { return f == kFilmFixed64 ? "fixed-point int64 (film_exact=1)" : "float32 (film_exact=0)"; }
-// Chains per chunk of the record stream (device staging -> pinned host -> file): as many as fit kCkptChunkBytes.  Neither side ever holds a second
-// copy of the population; 64 MiB is where the per-chunk costs (a launch, a copy, a stream wait) have vanished against the copy itself
-// (DESIGN.md "Checkpoint": the file is the bound, by an order of magnitude).
-constexpr size_t kCkptChunkBytes = (size_t)64 << 20;
-struct CkptHeader {
-    char magic[8];
-    uint32_t version, headerBytes;
-    // fingerprint
-    uint64_t sceneHash;
-    int32_t forceDiffuse, width, height, maxDepth, minDepth, seedOffset, useGradient, maxDervDepth;
-    int32_t mala, h2mc, sampleCache, useLightCoord, largeStepMultiplexed, filmFormat;  // filmFormat: kFilmFloat32 / kFilmFixed64 (the word was reserved and zero in version 1)
-    float largeStepProb, largeStepScale, malaStepsize, malaGN, perturbStdDev, uniformMixProb;
-    // the job's shape, progress
-    int32_t nChainsTotal, initThreads;
-    int64_t samplesPerChain, chainsNeedExtra, numInitSamples, stepsDone;
-    double wallSeconds;
-    // sizes
-    uint32_t recordWords, filmWords;
-    uint64_t jobBytes, totalBytes;
-};
-static_assert(sizeof(CkptHeader) == 176, "the checkpoint header is written as it lies in memory");
-
-uint64_t HashSceneFiles(const lmc::Scene &sc) {  // FNV-1a, 64 bit, over the bytes of the XML and of every file it pulled in, in parse order
-    uint64_t h = 1469598103934665603ull;
-    std::vector<unsigned char> buf(1 << 20);
-    for (const std::string &fn : sc.sourceFiles) {
-        FILE *f = fopen(fn.c_str(), "rb");
-        if (!f) throw std::runtime_error("checkpoint: cannot read the scene file " + fn + " for its content hash");
-        for (size_t n; (n = fread(buf.data(), 1, buf.size(), f)) > 0;)
-            for (size_t k = 0; k < n; k++) h = (h ^ buf[k]) * 1099511628211ull;
-        fclose(f);
-        h = (h ^ 0xffu) * 1099511628211ull;  // file boundary
-    }
-    return h;
-}
-CkptHeader MakeCkptHeader(lmc_ctx *c) {
-    CkptHeader H;
-    memset(&H, 0, sizeof(H));
-    memcpy(H.magic, kCkptMagic, 8);
-    H.version = c->filmExact ? kCkptVersionExact : kCkptVersion, H.headerBytes = sizeof(CkptHeader);
-    H.filmFormat = c->filmExact ? kFilmFixed64 : kFilmFloat32;
-    if (!c->sceneHash) c->sceneHash = HashSceneFiles(*c->scene);
-    const lmc::DptOptions &o = c->scene->options;
-    H.sceneHash = c->sceneHash;
-    H.forceDiffuse = c->forceDiffuse, H.width = c->S.cam.width, H.height = c->S.cam.height, H.maxDepth = o.maxDepth, H.minDepth = o.minDepth, H.seedOffset = o.seedOffset;
-    H.useGradient = c->useGradient, H.maxDervDepth = c->maxDervDepth;
-    H.mala = o.mala, H.h2mc = o.h2mc, H.sampleCache = o.sampleFromGlobalCache, H.useLightCoord = o.useLightCoordinateSampling, H.largeStepMultiplexed = o.largeStepMultiplexed;
-    H.largeStepProb = o.largeStepProbability, H.largeStepScale = o.largeStepProbScale, H.malaStepsize = o.malaStepsize, H.malaGN = o.malaGN;
-    H.perturbStdDev = o.perturbStdDev, H.uniformMixProb = o.uniformMixingProbability;
-    H.recordWords = (uint32_t)CkptRecordWords(o.maxDepth, c->S.opt.sampleCache != 0, o.h2mc);
-    H.filmWords = (uint32_t)c->film.n;
-    return H;
-}
-// the first fingerprint field in which the file differs from what the context would write; nullptr: none
-const char *CkptMismatch(const CkptHeader &f, const CkptHeader &c) {
-#define LMC_CK_FIELD(field, name) \
-    if (memcmp(&f.field, &c.field, sizeof(f.field)) != 0) return name;
-    LMC_CK_FIELD(sceneHash, "scene (the content hash of the scene XML and the files it pulls in)")
-    LMC_CK_FIELD(forceDiffuse, "force_diffuse")
-    LMC_CK_FIELD(width, "width")
-    LMC_CK_FIELD(height, "height")
-    LMC_CK_FIELD(maxDepth, "maxdepth")
-    LMC_CK_FIELD(minDepth, "mindepth")
-    LMC_CK_FIELD(seedOffset, "seedoffset")
-    LMC_CK_FIELD(useGradient, "use_gradient")
-    LMC_CK_FIELD(maxDervDepth, "max-derivatives-depth")
-    LMC_CK_FIELD(mala, "mala")
-    LMC_CK_FIELD(h2mc, "h2mc")
-    LMC_CK_FIELD(sampleCache, "samplecache")
-    LMC_CK_FIELD(useLightCoord, "uselightcoordinatesampling")
-    LMC_CK_FIELD(largeStepMultiplexed, "largestepmultiplexed")
-    LMC_CK_FIELD(largeStepProb, "largestepprob")
-    LMC_CK_FIELD(largeStepScale, "largestepscale")
-    LMC_CK_FIELD(malaStepsize, "mala-stepsize")
-    LMC_CK_FIELD(malaGN, "mala-gn")
-    LMC_CK_FIELD(perturbStdDev, "perturbstddev")
-    LMC_CK_FIELD(uniformMixProb, "uniformmixprob")
-    LMC_CK_FIELD(recordWords, "record size")
-    LMC_CK_FIELD(filmWords, "film size")
-#undef LMC_CK_FIELD
-    return nullptr;
-}
-struct CkptFile {
-    FILE *f = nullptr;
-    std::string path;
-    ~CkptFile() {
-        if (f) fclose(f);
-    }
-    void Open(const std::string &p, const char *mode) {
-        path = p;
-        f = fopen(p.c_str(), mode);
-        if (!f) throw std::runtime_error("checkpoint: cannot open " + p);
-    }
-    void Write(const void *p, size_t bytes) {
-        if (bytes && fwrite(p, 1, bytes, f) != bytes) throw std::runtime_error("checkpoint: short write to " + path);
-    }
-    void Read(void *p, size_t bytes) {
-        if (bytes && fread(p, 1, bytes, f) != bytes) throw std::runtime_error("checkpoint: " + path + " ends before its header says it does");
-    }
-    template <class T>
-    void WriteVec(const std::vector<T> &v) { Write(v.data(), v.size() * sizeof(T)); }
-    template <class T>
-    std::vector<T> ReadVec(size_t n) {
-        std::vector<T> v(n);
-        Read(v.data(), n * sizeof(T));
-        return v;
-    }
-};
-// header of `path`, checked as far as a file alone can be: magic, version, header size, and a length of at least what the header says
-CkptHeader ReadCkptHeader(CkptFile &F) {
-    CkptHeader H;
-    memset(&H, 0, sizeof(H));
-    if (fread(&H, 1, sizeof(H), F.f) != sizeof(H)) throw std::runtime_error("checkpoint: " + F.path + " is shorter than a checkpoint header");
-    if (memcmp(H.magic, kCkptMagic, 8) != 0) throw std::runtime_error("checkpoint: " + F.path + " is not a checkpoint file (wrong magic)");
-    if ((H.version != kCkptVersion && H.version != kCkptVersionExact) || H.headerBytes != sizeof(CkptHeader))
-        throw std::runtime_error("checkpoint: " + F.path + " has format version " + std::to_string(H.version) + ", this library reads version " + std::to_string(kCkptVersion) + " (and " +
-                                 std::to_string(kCkptVersionExact) + ", the exact film)");
-    if (H.filmFormat != (H.version == kCkptVersionExact ? kFilmFixed64 : kFilmFloat32)) throw std::runtime_error("checkpoint: " + F.path + " has an inconsistent header (film format)");
-    if (fseek(F.f, 0, SEEK_END) != 0) throw std::runtime_error("checkpoint: cannot seek in " + F.path);
-    const long long len = ftell(F.f);
-    if (H.nChainsTotal <= 0 || H.totalBytes != sizeof(CkptHeader) + H.jobBytes + (uint64_t)H.nChainsTotal * H.recordWords * sizeof(float))
-        throw std::runtime_error("checkpoint: " + F.path + " has an inconsistent header");
-    if (len < 0 || (uint64_t)len < H.totalBytes)
-        throw std::runtime_error("checkpoint: " + F.path + " is truncated: " + std::to_string(len) + " bytes, its header says " + std::to_string(H.totalBytes));
-    if (fseek(F.f, (long)sizeof(CkptHeader), SEEK_SET) != 0) throw std::runtime_error("checkpoint: cannot seek in " + F.path);
-    return H;
-}
-void CkptDrain(lmc_ctx *c) {  // the tail of the last step: cache pushes, the fill counts on their way to the host, a kd-tree going up on the cache stream
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    for (hipStream_t st : c->sideStream)
-        if (st) HIP_CHECK(hipStreamSynchronize(st));
-    for (hipStream_t st : c->partStream)
-        if (st) HIP_CHECK(hipStreamSynchronize(st));
-    if (c->cacheStream) HIP_CHECK(hipStreamSynchronize(c->cacheStream));
-}
-void CkptCheckMembers(const std::vector<lmc_ctx *> &g, const char *what, bool needChains) {
-    for (lmc_ctx *c : g) {
-        if (!c) throw std::runtime_error(std::string(what) + ": null context");
-        if (c->comm && c->world > 1) throw std::runtime_error(std::string(what) + ": this context is a rank of an RCCL job (lmc_comm_init); checkpoints serve single contexts and in-process groups only");
-        if (needChains && c->N <= 0) throw std::runtime_error(std::string(what) + " before lmc_chains_init");
-    }
-    if (needChains) {
-        if (g.size() == 1 && g[0]->group.size() > 1) throw std::runtime_error(std::string(what) + ": this context is a member of an in-process group, use the lmc_group_checkpoint_ call");
-        if (g.size() > 1)
-            for (lmc_ctx *c : g)
-                if (c->group != g) throw std::runtime_error(std::string(what) + ": not the group lmc_group_chains_init / lmc_group_checkpoint_load set up");
-    }
-}
-struct CkptTiming {
-    double packMs = 0, copyMs = 0, fileMs = 0;
-};
-double MsSince(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
-bool CkptLog() {
-    static const bool on = getenv("LMC_CKPT_LOG") != nullptr;  // measurement: the parts of a save / load, one line on stderr
-    return on;
-}
-
-void CkptSave(const std::vector<lmc_ctx *> &g, const char *path, const char *what) {
-    if (!path || !*path) throw std::runtime_error(std::string(what) + ": no path");
-    CkptCheckMembers(g, what, true);
-    for (lmc_ctx *c : g)
-        if (c->filmReduced) throw std::runtime_error(std::string(what) + ": the film already holds the sum over the ranks; a checkpoint of it would count the other ranks' share again");
-    const auto t0 = std::chrono::steady_clock::now();
-    for (lmc_ctx *c : g) CkptDrain(c);
-    lmc_ctx *c0 = g[0];
-    CkptHeader H = MakeCkptHeader(c0);
-    int next = 0;
-    for (lmc_ctx *c : g) {
-        if (c->chainBegin != next || c->numChainsTotal != c0->numChainsTotal) throw std::runtime_error(std::string(what) + ": the contexts do not hold one job's chains in order");
-        if (CkptMismatch(MakeCkptHeader(c), H)) throw std::runtime_error(std::string(what) + ": the members differ in " + CkptMismatch(MakeCkptHeader(c), H));
-        if (c->filmExact != c0->filmExact) throw std::runtime_error(std::string(what) + ": the members differ in film_exact");
-        next += c->N;
-    }
-    if (next != c0->numChainsTotal) throw std::runtime_error(std::string(what) + ": the contexts hold " + std::to_string(next) + " of the job's " + std::to_string(c0->numChainsTotal) + " chains");
-    H.nChainsTotal = c0->numChainsTotal, H.initThreads = c0->initThreads;
-    H.samplesPerChain = c0->perChain, H.chainsNeedExtra = c0->chainsNeedExtra, H.numInitSamples = c0->numInitSamples, H.stepsDone = c0->stepsDone;
-    H.wallSeconds = c0->secondsBefore + std::chrono::duration<double>(std::chrono::steady_clock::now() - c0->chainsSince).count();
-    // ---- job-wide state, from member 0 (identical on all members) except what the members hold a share of: counters, weight sum, film
-    HIP_CHECK(hipSetDevice(c0->device));
-    std::vector<char> job;
-    auto put = [&](const void *p, size_t bytes) { job.insert(job.end(), (const char *)p, (const char *)p + bytes); };
-    const int32_t lengthCount = (int32_t)c0->lengthFunc.size();
-    const int64_t numInitContribs = c0->numInitContribs;
-    put(&c0->normalization, 4), put(&c0->lengthFuncInt, 4), put(&numInitContribs, 8), put(&lengthCount, 4), put(&lengthCount, 4);
-    put(c0->lengthFunc.data(), c0->lengthFunc.size() * 4), put(c0->lengthCdf.data(), c0->lengthCdf.size() * 4);
-    {
-        const std::vector<float> ls = c0->initLsAll.Download();
-        std::vector<unsigned char> cl = c0->initCLAll.Download();
-        cl.resize((cl.size() + 3) / 4 * 4, 0);
-        put(ls.data(), ls.size() * 4), put(cl.data(), cl.size());
-    }
-    const std::vector<int> counts = c0->cacheCounts.Download();
-    for (int sl = 0; sl < CACHE_SLOTS; sl++) {
-        const CacheDimHost &cd = c0->cacheDims[6 + 2 * sl];
-        const int32_t head[4] = {cd.relevant ? 1 : 0, cd.relevant ? counts[sl] : 0, cd.ready ? 1 : 0, 6 + 2 * sl};
-        put(head, sizeof(head));
-        if (!cd.relevant) continue;
-        for (const DevBuf<float> *b : {&cd.pss, &cd.v1, &cd.v2, &cd.weight, &cd.extra}) {
-            const std::vector<float> v = b->Download();
-            put(v.data(), v.size() * 4);
-        }
-    }
-    {
-        std::vector<unsigned long long> counters(8, 0);
-        double weightSum = 0;
-        std::vector<float> film(c0->filmExact ? 0 : c0->film.n, 0.f);
-        std::vector<long long> filmFx(c0->filmExact ? c0->film.n + 1 : 0, 0);  // exact mode: summed in int64; the film_overflow counter is the word behind the film, as on the device
-        for (lmc_ctx *c : g) {  // rank order, like the film merge
-            HIP_CHECK(hipSetDevice(c->device));
-            const std::vector<unsigned long long> cc = c->counters.Download();
-            for (int k = 0; k < 8; k++) counters[k] += cc[k];
-            weightSum += c->weightSum.Download()[0];
-            if (c0->filmExact) {
-                const std::vector<long long> f = c->filmFx.Download();
-                if (f.size() != filmFx.size()) throw std::runtime_error(std::string(what) + ": the members' films differ in size");
-                for (size_t k = 0; k < filmFx.size(); k++) filmFx[k] += f[k];
-                continue;
-            }
-            const std::vector<float> f = c->film.Download();
-            if (f.size() != film.size()) throw std::runtime_error(std::string(what) + ": the members' films differ in size");
-            for (size_t k = 0; k < f.size(); k++) film[k] += f[k];
-        }
-        put(counters.data(), 64), put(&weightSum, 8), put(film.data(), film.size() * 4), put(filmFx.data(), filmFx.size() * 8);
-    }
-    H.jobBytes = job.size();
-    H.totalBytes = sizeof(CkptHeader) + H.jobBytes + (uint64_t)H.nChainsTotal * H.recordWords * sizeof(float);
-    const std::string tmp = std::string(path) + ".tmp";
-    CkptTiming T;
-    {
-        CkptFile F;
-        F.Open(tmp, "wb");
-        auto tf = std::chrono::steady_clock::now();
-        F.Write(&H, sizeof(H)), F.Write(job.data(), job.size());
-        T.fileMs += MsSince(tf);
-        // ---- the records, member by member = in chain order, a chunk at a time
-        const size_t recBytes = (size_t)H.recordWords * sizeof(float);
-        for (lmc_ctx *c : g) {
-            HIP_CHECK(hipSetDevice(c->device));
-            const int chunk = (int)std::min<size_t>((size_t)c->N, std::max<size_t>(1024, kCkptChunkBytes / recBytes));
-            DevBuf<float> staging;
-            staging.Alloc((size_t)chunk * H.recordWords, false);
-            float *pinned = nullptr;
-            HIP_CHECK(hipHostMalloc((void **)&pinned, (size_t)chunk * recBytes, hipHostMallocDefault));
-            try {
-                for (int first = 0; first < c->N; first += chunk) {
-                    const int n = std::min(chunk, c->N - first);
-                    auto tp = std::chrono::steady_clock::now();
-                    LaunchCkptPack(c->A, c->S.opt.maxDepth, c->S.opt.sampleCache != 0, c->S.opt.h2mc ? c->h2Gauss.p : nullptr, first, n, staging.p, c->stream);
-                    HIP_CHECK(hipGetLastError());
-                    if (CkptLog()) HIP_CHECK(hipStreamSynchronize(c->stream));
-                    T.packMs += MsSince(tp);
-                    tp = std::chrono::steady_clock::now();
-                    HIP_CHECK(hipMemcpyAsync(pinned, staging.p, (size_t)n * recBytes, hipMemcpyDeviceToHost, c->stream));
-                    HIP_CHECK(hipStreamSynchronize(c->stream));
-                    T.copyMs += MsSince(tp);
-                    tp = std::chrono::steady_clock::now();
-                    F.Write(pinned, (size_t)n * recBytes);
-                    T.fileMs += MsSince(tp);
-                }
-            } catch (...) {
-                (void)hipHostFree(pinned);
-                throw;
-            }
-            (void)hipHostFree(pinned);
-        }
-        auto tp = std::chrono::steady_clock::now();
-        if (fflush(F.f) != 0) throw std::runtime_error(std::string(what) + ": cannot flush " + tmp);
-        T.fileMs += MsSince(tp);
-    }
-    if (rename(tmp.c_str(), path) != 0) throw std::runtime_error(std::string(what) + ": cannot rename " + tmp + " to " + path);
-    if (CkptLog())
-        fprintf(stderr, "[lmc] checkpoint save: %d chains, %llu bytes, %u bytes per chain record: pack %.3f ms, copies %.3f ms, file %.3f ms, total %.3f ms\n", H.nChainsTotal,
-                (unsigned long long)H.totalBytes, H.recordWords * 4u, T.packMs, T.copyMs, T.fileMs, MsSince(t0));
-}
-
-void CkptLoad(const std::vector<lmc_ctx *> &g, const char *path, const char *what) {
-    if (!path || !*path) throw std::runtime_error(std::string(what) + ": no path");
-    if (g.empty()) throw std::runtime_error(std::string(what) + ": empty group");
-    CkptCheckMembers(g, what, false);
-    const auto t0 = std::chrono::steady_clock::now();
-    CkptFile F;
-    F.Open(path, "rb");
-    const CkptHeader H = ReadCkptHeader(F);
-    for (lmc_ctx *c : g) {
-        if (const char *field = CkptMismatch(H, MakeCkptHeader(c))) throw std::runtime_error(std::string(what) + ": " + path + " was written for another render: '" + field + "' differs");
-        if (H.filmFormat != (c->filmExact ? kFilmFixed64 : kFilmFloat32))
-            throw std::runtime_error(std::string(what) + ": " + path + " holds a " + FilmFormatName(H.filmFormat) + " film, this context's film is " + FilmFormatName(c->filmExact ? kFilmFixed64 : kFilmFloat32) +
-                                     "; set the film_exact option to the file's mode before loading");
-    }
-    if ((size_t)H.nChainsTotal < g.size()) throw std::runtime_error(std::string(what) + ": fewer chains than members");
-    // ---- the job-wide state, on the host (a few MB); everything up to here has left the contexts as they were
-    std::vector<char> job(H.jobBytes);
-    F.Read(job.data(), job.size());
-    size_t at = 0;
-    auto get = [&](void *p, size_t bytes) {
-        if (at + bytes > job.size()) throw std::runtime_error(std::string(what) + ": " + path + " has a job-wide section shorter than its contents");
-        memcpy(p, job.data() + at, bytes);
-        at += bytes;
-    };
-    float normalization = 0, lengthFuncInt = 0;
-    int64_t numInitContribs = 0;
-    int32_t lengthCount = 0, lengthCount2 = 0;
-    get(&normalization, 4), get(&lengthFuncInt, 4), get(&numInitContribs, 8), get(&lengthCount, 4), get(&lengthCount2, 4);
-    if (lengthCount < 0 || lengthCount > LENGTH_DIST_MAX) throw std::runtime_error(std::string(what) + ": bad length distribution in " + path);
-    std::vector<float> lengthFunc(lengthCount), lengthCdf(lengthCount + 1), seedLs(H.nChainsTotal);
-    std::vector<unsigned char> seedCL(((size_t)H.nChainsTotal + 3) / 4 * 4);
-    get(lengthFunc.data(), lengthFunc.size() * 4), get(lengthCdf.data(), lengthCdf.size() * 4), get(seedLs.data(), seedLs.size() * 4), get(seedCL.data(), seedCL.size());
-    seedCL.resize(H.nChainsTotal);
-    struct DimRows {
-        int32_t head[4] = {0, 0, 0, 0};  // relevant, rows filled, ready, dim
-        std::vector<float> rows[5];      // pss, v1, v2, weight, extra
-    } dims[CACHE_SLOTS];
-    const bool sampleCache = g[0]->S.opt.sampleCache != 0;
-    for (int sl = 0; sl < CACHE_SLOTS; sl++) {
-        const int d = 6 + 2 * sl;
-        get(dims[sl].head, sizeof(dims[sl].head));
-        if (dims[sl].head[3] != d) throw std::runtime_error(std::string(what) + ": bad cache section in " + path);
-        if (!dims[sl].head[0]) continue;
-        const size_t n[5] = {(size_t)PSS_MAX_SIZE * d, (size_t)PSS_MAX_SIZE * d, (size_t)PSS_MAX_SIZE * d, (size_t)PSS_MAX_SIZE, sampleCache ? (size_t)PSS_MAX_SIZE * CACHE_ROW_EXTRA : 0};
-        for (int k = 0; k < 5; k++) dims[sl].rows[k].resize(n[k]), get(dims[sl].rows[k].data(), n[k] * 4);
-    }
-    std::vector<unsigned long long> counters(8);
-    double weightSum = 0;
-    const bool exact = H.filmFormat == kFilmFixed64;
-    std::vector<float> film(exact ? 0 : H.filmWords);
-    std::vector<long long> filmFx(exact ? (size_t)H.filmWords + 1 : 0);
-    get(counters.data(), 64), get(&weightSum, 8), get(film.data(), film.size() * 4);
-    if (exact) get(filmFx.data(), filmFx.size() * 8);  // the words, then the film_overflow counter
-    // the kd-trees of the dims the file holds ready: rebuilt from the rows by the code that built them (deterministic), once for all members
-    lmc::KdTreeResult trees[CACHE_SLOTS];
-    for (int sl = 0; sl < CACHE_SLOTS; sl++)
-        if (dims[sl].head[0] && dims[sl].head[2]) trees[sl] = lmc::BuildKdTree(dims[sl].rows[0].data(), PSS_MAX_SIZE, 6 + 2 * sl);
-    // ---- from here on the contexts change
-    const size_t n = g.size();
-    const size_t recBytes = (size_t)H.recordWords * sizeof(float);
-    const uint64_t recordsAt = sizeof(CkptHeader) + H.jobBytes;
-    CkptTiming T;
-    try {
-        if (n > 1 || g[0]->group.size() > 1)
-            for (size_t r = 0; r < n; r++) {
-                for (lmc_ctx *peer : g[r]->group)  // leaving an earlier group (lmc_group_chains_init does the same)
-                    if (peer != g[r]) peer->group.clear(), peer->world = 1, peer->rank = 0;
-                g[r]->world = (int)n, g[r]->rank = (int)r, g[r]->group = n > 1 ? g : std::vector<lmc_ctx *>();
-            }
-        for (size_t r = 0; r < n; r++) {
-            lmc_ctx *c = g[r];
-            ChainSetUp U;
-            U.numChainsTotal = H.nChainsTotal, U.chainBegin = (int)((long long)H.nChainsTotal * (long long)r / (long long)n), U.chainEnd = (int)((long long)H.nChainsTotal * (long long)(r + 1) / (long long)n);
-            U.perChain = H.samplesPerChain, U.chainsNeedExtra = H.chainsNeedExtra, U.seedLs = &seedLs, U.seedCL = &seedCL, U.fromCheckpoint = true;
-            // before the set-up: its warm launches take their parameters (MakeStepParams: the length distribution) from the context
-            c->normalization = normalization, c->lengthFuncInt = lengthFuncInt, c->numInitContribs = numInitContribs, c->lengthFunc = lengthFunc, c->lengthCdf = lengthCdf;
-            SetUpChains(c, U);
-            hipStream_t s = c->stream;
-            c->initCL.clear(), c->initLs.clear(), c->initOffsets.clear();  // the per-contribution lists of MLTInit (lmc_init_contribs) are not part of a checkpoint
-            c->numInitSamples = H.numInitSamples, c->initThreads = H.initThreads;
-            // the caches: rows and fill counts as they were; a ready dim's existence grid built on the device, its tree uploaded, the struct published
-            int cnt[CACHE_SLOTS] = {0, 0, 0, 0};
-            bool anyReady = false;
-            for (int sl = 0; sl < CACHE_SLOTS; sl++) {
-                const int d = 6 + 2 * sl;
-                CacheDimHost &cd = c->cacheDims[d];
-                if ((dims[sl].head[0] != 0) != cd.relevant) throw std::runtime_error(std::string(what) + ": the file's cache dims are not this render's");
-                if (!cd.relevant) continue;
-                DevBuf<float> *dst[5] = {&cd.pss, &cd.v1, &cd.v2, &cd.weight, &cd.extra};
-                for (int k = 0; k < 5; k++)
-                    if (!dims[sl].rows[k].empty()) HIP_CHECK(hipMemcpy(dst[k]->p, dims[sl].rows[k].data(), dims[sl].rows[k].size() * 4, hipMemcpyHostToDevice));
-                cnt[sl] = dims[sl].head[1], c->lastCounts[sl] = cnt[sl];
-                if (!dims[sl].head[2]) continue;
-                const lmc::KdTreeResult &t = trees[sl];
-                if (t.nodes.size() > KD_MAX_NODES || t.vind.size() > (size_t)PSS_MAX_SIZE) throw std::runtime_error("kd-tree larger than its preallocated buffers");
-                lmc::ChooseGridCoords(dims[sl].rows[0].data(), PSS_MAX_SIZE, d, cd.gridM, cd.gridCoord);
-                LaunchBuildCacheGrid(cd.pss.p, PSS_MAX_SIZE, d, cd.gridG, cd.gridM, cd.gridCoord, c->gridScratchStart.p, c->gridScratchCursor.p, c->gridScratchWordCount.p, c->gridTileSums.p,
-                                     cd.gridWords.p, cd.gridCellStart.p, cd.gridIdx.p, s);
-                HIP_CHECK(hipMemcpyAsync(cd.nodes.p, t.nodes.data(), t.nodes.size() * sizeof(KdNode), hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(cd.vind.p, t.vind.data(), t.vind.size() * sizeof(int), hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                PublishCacheDim(c, d, t, s);
-                cd.ready = true, anyReady = true;
-            }
-            HIP_CHECK(hipMemcpy(c->cacheCounts.p, cnt, sizeof(cnt), hipMemcpyHostToDevice));
-            if (anyReady) UploadCacheStruct(c);
-            if (r == 0) {  // the film, the counters and the weight sum go to member 0 alone: the film merge stays a sum
-                HIP_CHECK(hipMemcpy(c->counters.p, counters.data(), 64, hipMemcpyHostToDevice));
-                HIP_CHECK(hipMemcpy(c->weightSum.p, &weightSum, 8, hipMemcpyHostToDevice));
-                if (exact) HIP_CHECK(hipMemcpy(c->filmFx.p, filmFx.data(), filmFx.size() * 8, hipMemcpyHostToDevice));
-                else
-                    HIP_CHECK(hipMemcpy(c->film.p, film.data(), film.size() * 4, hipMemcpyHostToDevice));
-            }
-            // the records of this member's chains
-            const int chunk = (int)std::min<size_t>((size_t)c->N, std::max<size_t>(1024, kCkptChunkBytes / recBytes));
-            DevBuf<float> staging;
-            staging.Alloc((size_t)chunk * H.recordWords, false);
-            float *pinned = nullptr;
-            HIP_CHECK(hipHostMalloc((void **)&pinned, (size_t)chunk * recBytes, hipHostMallocDefault));
-            try {
-                if (fseeko(F.f, (off_t)(recordsAt + (uint64_t)c->chainBegin * recBytes), SEEK_SET) != 0) throw std::runtime_error(std::string(what) + ": cannot seek in " + path);
-                for (int first = 0; first < c->N; first += chunk) {
-                    const int m = std::min(chunk, c->N - first);
-                    auto tp = std::chrono::steady_clock::now();
-                    F.Read(pinned, (size_t)m * recBytes);
-                    T.fileMs += MsSince(tp);
-                    tp = std::chrono::steady_clock::now();
-                    HIP_CHECK(hipMemcpyAsync(staging.p, pinned, (size_t)m * recBytes, hipMemcpyHostToDevice, s));
-                    if (CkptLog()) HIP_CHECK(hipStreamSynchronize(s));
-                    T.copyMs += MsSince(tp);
-                    tp = std::chrono::steady_clock::now();
-                    LaunchCkptUnpack(c->A, c->S.opt.maxDepth, sampleCache, c->S.opt.h2mc ? c->h2Gauss.p : nullptr, first, m, staging.p, s);
-                    HIP_CHECK(hipGetLastError());
-                    HIP_CHECK(hipStreamSynchronize(s));
-                    T.packMs += MsSince(tp);
-                }
-            } catch (...) {
-                (void)hipHostFree(pinned);
-                throw;
-            }
-            (void)hipHostFree(pinned);
-            // the work lists of the step that runs next, from the chains' nextKind and the caches as they are now (what the step before the save built)
-            HIP_CHECK(hipMemsetAsync(c->listCounts[0].p, 0, 4 * sizeof(int), s));
-            if (!c->allCachesReady) CachePending(c);  // allCachesReady / needGeneric as the head of the next step would find them
-            BuildNextLists(c, 0);
-            c->parity = 0;
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipGetLastError());
-            c->stepsDone = H.stepsDone, c->secondsBefore = H.wallSeconds, c->chainsSince = std::chrono::steady_clock::now();
-        }
-        if (n > 1) GroupSetUpMerge(g);
-    } catch (...) {  // a load that failed half way leaves no chains behind
-        for (lmc_ctx *c : g) c->group.clear(), c->world = 1, c->rank = 0, c->N = 0;
-        throw;
-    }
-    if (CkptLog())
-        fprintf(stderr, "[lmc] checkpoint load: %d chains, %llu bytes: file %.3f ms, copies %.3f ms, unpack %.3f ms, total %.3f ms (set-up, cache trees and lists included)\n", H.nChainsTotal,
-                (unsigned long long)H.totalBytes, T.fileMs, T.copyMs, T.packMs, MsSince(t0));
-}
-}  // namespace
-}  // extern "C++"
-
-int lmc_checkpoint_save(lmc_ctx *c, const char *path) {
-    LMC_TRY
-    CkptSave({c}, path, "lmc_checkpoint_save");
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_checkpoint_load(lmc_ctx *c, const char *path) {
-    LMC_TRY
-    if (c && c->group.size() > 1) throw std::runtime_error("lmc_checkpoint_load: this context is a member of an in-process group, use lmc_group_checkpoint_load");
-    CkptLoad({c}, path, "lmc_checkpoint_load");
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_group_checkpoint_save(lmc_ctx **ctxs, int n, const char *path) {
-    LMC_TRY
-    if (n < 1) throw std::runtime_error("lmc_group_checkpoint_save: empty group");
-    CkptSave(std::vector<lmc_ctx *>(ctxs, ctxs + n), path, "lmc_group_checkpoint_save");
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_group_checkpoint_load(lmc_ctx **ctxs, int n, const char *path) {
-    LMC_TRY
-    if (n < 1) throw std::runtime_error("lmc_group_checkpoint_load: empty group");
-    CkptLoad(std::vector<lmc_ctx *>(ctxs, ctxs + n), path, "lmc_group_checkpoint_load");
-    return 0;
-    LMC_CATCH(-1)
-}
-// host only: the header of a checkpoint file as one JSON document (lmc_scene_dump's convention: at most cap - 1 characters + NUL, returns the full length, -1 on error)
-long long lmc_checkpoint_info(const char *path, char *out, long long cap) {
-    LMC_TRY
-    if (!path) throw std::runtime_error("lmc_checkpoint_info: no path");
-    CkptFile F;
-    F.Open(path, "rb");
-    const CkptHeader H = ReadCkptHeader(F);
-    char buf[2048];
-    snprintf(buf, sizeof(buf),
-             "{\"version\":%u,\"film_format\":\"%s\",\"scene_hash\":\"%016llx\",\"force_diffuse\":%d,\"width\":%d,\"height\":%d,\"maxdepth\":%d,\"mindepth\":%d,\"seedoffset\":%d,\"use_gradient\":%d,"
-             "\"max-derivatives-depth\":%d,\"mala\":%d,\"h2mc\":%d,\"samplecache\":%d,\"uselightcoordinatesampling\":%d,\"largestepmultiplexed\":%d,\"largestepprob\":%.9g,"
-             "\"largestepscale\":%.9g,\"mala-stepsize\":%.9g,\"mala-gn\":%.9g,\"perturbstddev\":%.9g,\"uniformmixprob\":%.9g,\"n_chains_total\":%d,\"samples_per_chain\":%lld,"
-             "\"chains_need_extra\":%lld,\"num_init_samples\":%lld,\"init_threads\":%d,\"steps_done\":%lld,\"wall_seconds\":%.9g,\"record_bytes\":%u,\"job_bytes\":%llu,\"total_bytes\":%llu}",
-             H.version, H.filmFormat == kFilmFixed64 ? "fixed64" : "float32", (unsigned long long)H.sceneHash, H.forceDiffuse, H.width, H.height, H.maxDepth, H.minDepth, H.seedOffset, H.useGradient, H.maxDervDepth, H.mala, H.h2mc, H.sampleCache,
-             H.useLightCoord, H.largeStepMultiplexed, H.largeStepProb, H.largeStepScale, H.malaStepsize, H.malaGN, H.perturbStdDev, H.uniformMixProb, H.nChainsTotal, (long long)H.samplesPerChain,
-             (long long)H.chainsNeedExtra, (long long)H.numInitSamples, H.initThreads, (long long)H.stepsDone, H.wallSeconds, H.recordWords * 4u, (unsigned long long)H.jobBytes,
-             (unsigned long long)H.totalBytes);
-    const std::string j(buf);
-    if (out && cap > 0) {
-        const size_t n = std::min<size_t>(j.size(), (size_t)cap - 1);
-        memcpy(out, j.data(), n);
-        out[n] = 0;
-    }
-    return (long long)j.size();
-    LMC_CATCH(-1)
-}
-
-// ---- batched path program (context-free)
-int lmc_grad_batch(int c, int l, int n, const float *primarySoA, const float *scene38, const float *vertSoA, float *loglum, float *gradSoA) {
-    LMC_TRY
-    if (!(c >= 1 && l >= 0 && c + l >= 3 && c + l - 1 <= 8)) throw std::runtime_error("lmc_grad_batch: technique (c,l) out of range");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) EnsureDevice(0);
-    else EnsureDevice(dev);
-    const int L = std::max(c + l - 1, 2), V = 238 + 59 * (c + l - 3);
-    DevBuf<float> dPrim, dScene, dVert, dLL, dGrad;
-    dPrim.Upload(primarySoA, (size_t)(2 * L + 1) * n), dScene.Upload(scene38, 38), dVert.Upload(vertSoA, (size_t)V * n);
-    dLL.Alloc(n), dGrad.Alloc((size_t)2 * L * n);
-    LaunchGradBatch(c, l, n, dPrim.p, dScene.p, dVert.p, dLL.p, dGrad.p, gradSoA ? 1 : 0, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (loglum) HIP_CHECK(hipMemcpy(loglum, dLL.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (gradSoA) HIP_CHECK(hipMemcpy(gradSoA, dGrad.p, (size_t)2 * L * n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// gradient + Hessian batch (H2MC): hess_soa[(2L)^2 * n], entry (i,k) of item j at [(i * 2L + k) * n + j]
-int lmc_hess_batch(int c, int l, int n, const float *primarySoA, const float *scene38, const float *vertSoA, float *loglum, float *gradSoA, float *hessSoA) {
-    LMC_TRY
-    if (!(c >= 1 && l >= 0 && c + l >= 3 && c + l - 1 <= 8)) throw std::runtime_error("lmc_hess_batch: technique (c,l) out of range");
-    if (!hessSoA) throw std::runtime_error("lmc_hess_batch: null output");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) EnsureDevice(0);
-    else EnsureDevice(dev);
-    const int L = std::max(c + l - 1, 2), V = 238 + 59 * (c + l - 3), dim = 2 * L;
-    DevBuf<float> dPrim, dScene, dVert, dLL, dGrad, dHess;
-    dPrim.Upload(primarySoA, (size_t)(2 * L + 1) * n), dScene.Upload(scene38, 38), dVert.Upload(vertSoA, (size_t)V * n);
-    dLL.Alloc(n), dGrad.Alloc((size_t)dim * n), dHess.Alloc((size_t)dim * dim * n);
-    LaunchHessBatch(c, l, n, dPrim.p, dScene.p, dVert.p, dLL.p, dGrad.p, dHess.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (loglum) HIP_CHECK(hipMemcpy(loglum, dLL.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (gradSoA) HIP_CHECK(hipMemcpy(gradSoA, dGrad.p, (size_t)dim * n * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(hessSoA, dHess.p, (size_t)dim * dim * n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// ---- probes
-// exp / log / pow of device/dtrans.h on the device (mode 0 / 1 / 2): the GPU side of the bit-equality test against the host build
-int lmc_trans_probe(int n, int mode, const float *x, const float *y, float *out) {
-    LMC_TRY
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) EnsureDevice(0);
-    else EnsureDevice(dev);
-    DevBuf<float> dx, dy, dout;
-    dx.Upload(x, n), dy.Upload(y, n), dout.Alloc(n);
-    LaunchTransProbe(n, mode, dx.p, dy.p, dout.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_trace(lmc_ctx *c, int n, const float *rays, int *prim, float *t) {
-    LMC_TRY
-    DevBuf<float> dR, dT;
-    DevBuf<int> dP;
-    dR.Upload(rays, (size_t)n * 8), dT.Alloc(n), dP.Alloc(n);
-    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 0, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(prim, dP.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(t, dT.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_occluded(lmc_ctx *c, int n, const float *rays, int *occ) {
-    LMC_TRY
-    DevBuf<float> dR, dT;
-    DevBuf<int> dP;
-    dR.Upload(rays, (size_t)n * 8), dT.Alloc(n), dP.Alloc(n);
-    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 1, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(occ, dP.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_rng_probe(int nSeeds, const unsigned long long *seeds, int mode, int n, float mean, float stddev, unsigned *out) {
-    LMC_TRY
-    EnsureDevice(0);
-    DevBuf<unsigned long long> dS;
-    DevBuf<uint32_t> dTab, dOut;
-    dS.Upload(seeds, nSeeds), dTab.Alloc((size_t)nSeeds * 64), dOut.Alloc((size_t)nSeeds * (n + 66));
-    LaunchRngProbe(nSeeds, dS.p, mode, n, mean, stddev, dTab.p, dOut.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, dOut.p, dOut.n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-// test hook: the device's nine-way monotone search over cdf[0..n) for nq keys (tests compare with numpy.searchsorted)
-int lmc_lower_bound_probe(int n, const float *cdf, int nq, const float *u, int *out) {
-    LMC_TRY
-    EnsureDevice(0);
-    DevBuf<float> dC, dU;
-    DevBuf<int> dO;
-    dC.Upload(cdf, n), dU.Upload(u, nq), dO.Alloc(nq);
-    LaunchLowerBoundProbe(n, dC.p, nq, dU.p, dO.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, dO.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_stream_probe(long long nWords, int reps) {
-    LMC_TRY
-    EnsureDevice(0);
-    DevBuf<float> a, b;
-    a.Alloc((size_t)nWords), b.Alloc((size_t)nWords, false);
-    for (int r = 0; r < reps; r++) LaunchStreamProbe(nWords, a.p, b.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    return 0;
-    LMC_CATCH(-1)
-}
-// measurement aid: milliseconds per launch of the state-layout probe (kernels.hip k_layout_probe)
-int lmc_layout_probe(int nChains, int words, int mode, int batch, int reps, double *msPerLaunch) {
-    LMC_TRY
-    EnsureDevice(0);
-    DevBuf<float> a, b;
-    a.Alloc((size_t)nChains * words), b.Alloc((size_t)nChains * words, false);
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    LaunchLayoutProbe(nChains, words, mode, batch, a.p, b.p, 0);
-    HIP_CHECK(hipEventRecord(e0, 0));
-    for (int r = 0; r < reps; r++) LaunchLayoutProbe(nChains, words, mode, batch, a.p, b.p, 0);
-    HIP_CHECK(hipEventRecord(e1, 0));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *msPerLaunch = ms / reps;
-    HIP_CHECK(hipEventDestroy(e0));
-    HIP_CHECK(hipEventDestroy(e1));
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_kd_probe(int dim, int npts, const float *pts, int nq, const float *q, float radiusSq, int knn, int *outN, int *outIdx, float *outDist) {
-    LMC_TRY
-    EnsureDevice(0);
-    if (dim < 1 || dim > MAXPSS || knn > 8) throw std::runtime_error("lmc_kd_probe: bad arguments");
-    lmc::KdTreeResult t = lmc::BuildKdTree(pts, npts, dim);
-    DevBuf<KdNode> dN;
-    DevBuf<int> dV, dOutN, dOutI;
-    DevBuf<float> dP, dQ, dOutD;
-    dN.Upload(t.nodes), dV.Upload(t.vind), dP.Upload(pts, (size_t)npts * dim), dQ.Upload(q, (size_t)nq * dim);
-    dOutN.Alloc(nq), dOutI.Alloc((size_t)nq * knn), dOutD.Alloc((size_t)nq * knn);
-    DCacheDim C;
-    memset(&C, 0, sizeof(C));
-    C.ready = 1, C.nodes = dN.p, C.vind = dV.p, C.pts = dP.p, C.v1 = dP.p, C.v2 = dP.p;
-    for (int k = 0; k < dim; k++) C.rootLow[k] = t.rootLow[k], C.rootHigh[k] = t.rootHigh[k];
-    LaunchKdProbe(C, dim, nq, dQ.p, radiusSq, knn, dOutN.p, dOutI.p, dOutD.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(outN, dOutN.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(outIdx, dOutI.p, (size_t)nq * knn * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(outDist, dOutD.p, (size_t)nq * knn * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-// parity probe: the rows of one cache dim as they stand (pss: PSS_MAX_SIZE x dim, weight: PSS_MAX_SIZE, extra: PSS_MAX_SIZE x
-// CACHE_ROW_EXTRA = every row's DPath words followed by its Contrib words, only with `samplecache`; any pointer may be NULL).
-// Returns the number of rows filled, -1 on error.
-// test probe: n caller-given splats through the device's Splat (dchain.h) into a fresh W x H film, one launch of n lanes in 64-thread blocks.
-// exact != 0: out_fixed receives the W*H*3 fixed-point words, *overflow the dropped splats; out_float the film as lmc_film_read returns it
-// (exact: converted from the words on the device).  Any of the three outputs may be NULL.
-int lmc_film_splat_probe(int W, int H, int n, const float *screen_xy, const float *rgb, int exact, long long *out_fixed, float *out_float, long long *overflow) {
-    LMC_TRY
-    EnsureDevice(0);
-    if (W <= 0 || H <= 0 || n < 0 || (long long)W * H > (1ll << 26)) throw std::runtime_error("lmc_film_splat_probe: bad film size or splat count");
-    const size_t words = (size_t)W * H * 3;
-    DevBuf<float> dXY, dRGB, dFilm;
-    DevBuf<long long> dFx;
-    dXY.Upload(screen_xy, (size_t)n * 2), dRGB.Upload(rgb, (size_t)n * 3), dFilm.Alloc(words);
-    if (exact) dFx.Alloc(words + 1);
-    if (n > 0) LaunchFilmSplatProbe(exact ? FilmFx(dFx.p, W, H) : Film{dFilm.p, W, H}, n, dXY.p, dRGB.p, 0);
-    if (exact) LaunchFilmFixedToFloat(dFx.p, dFilm.p, words, 0);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    if (out_float) HIP_CHECK(hipMemcpy(out_float, dFilm.p, words * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_fixed) {
-        if (!exact) throw std::runtime_error("lmc_film_splat_probe: the fixed-point words exist in exact mode only");
-        HIP_CHECK(hipMemcpy(out_fixed, dFx.p, words * sizeof(long long), hipMemcpyDeviceToHost));
-    }
-    if (overflow) {
-        *overflow = 0;
-        if (exact) HIP_CHECK(hipMemcpy(overflow, dFx.p + words, sizeof(long long), hipMemcpyDeviceToHost));
-    }
-    return 0;
-    LMC_CATCH(-1)
-}
-
-int lmc_cache_rows(lmc_ctx *c, int dim, float *pss, float *weight, float *extra) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (dim < 6 || dim > PSS_MAX_LENGTH || (dim & 1) || !c->cacheDims[dim].relevant) return -1;
-    CacheDimHost &cd = c->cacheDims[dim];
-    if (pss) HIP_CHECK(hipMemcpy(pss, cd.pss.p, (size_t)PSS_MAX_SIZE * dim * sizeof(float), hipMemcpyDeviceToHost));
-    if (weight) HIP_CHECK(hipMemcpy(weight, cd.weight.p, (size_t)PSS_MAX_SIZE * sizeof(float), hipMemcpyDeviceToHost));
-    if (extra) {
-        if (!cd.extra.p) return -1;
-        HIP_CHECK(hipMemcpy(extra, cd.extra.p, (size_t)PSS_MAX_SIZE * CACHE_ROW_EXTRA * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    int counts[CACHE_SLOTS];
-    HIP_CHECK(hipMemcpy(counts, c->cacheCounts.p, sizeof(counts), hipMemcpyDeviceToHost));
-    return counts[(dim - 6) / 2];
-    LMC_CATCH(-1)
-}
-// parity probe of LargeStepCache's cache-side pieces on the device (`samplecache`, the dim must be ready): row[i] = sampleCache with
-// the uniform u[i] (global_cache.h:126-137), pdf[i] = evalPdfCache(query[i * dim ..], technique cl[2 i], cl[2 i + 1]) (:139-164).
-// Returns 0, -2 when the dim is not ready or the option is off, -1 on error.
-int lmc_cache_probe(lmc_ctx *c, int dim, int n, const float *u, int *row, const float *query, const int *cl, float *pdf) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (dim < 6 || dim > PSS_MAX_LENGTH || (dim & 1) || !c->cacheDims[dim].ready || !c->S.opt.sampleCache || !c->cacheDims[dim].extra.p) return -2;
-    DevBuf<float> du, dq, dp;
-    DevBuf<int> dr, dcl;
-    du.Upload(u, n), dq.Upload(query, (size_t)n * dim), dcl.Upload(cl, (size_t)2 * n), dr.Alloc(n), dp.Alloc(n);
-    LaunchCacheProbe(c->cacheDev.p, dim, n, du.p, dr.p, dq.p, dcl.p, dp.p, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipMemcpy(row, dr.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(pdf, dp.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-// checker of the device-built grid of one cache dim against the host build (accel.cpp): returns the number of cells whose row
-// sets differ (0 = identical), -1 on error, -2 when that dim's cache is not ready
-int lmc_cache_grid_check(lmc_ctx *c, int dim) {
-    LMC_TRY
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (dim < 0 || dim > PSS_MAX_LENGTH || !c->cacheDims[dim].ready) return -2;
-    CacheDimHost &cd = c->cacheDims[dim];
-    std::vector<float> pts = cd.pss.Download();
-    lmc::CacheGrid g = lmc::BuildCacheGrid(pts.data(), PSS_MAX_SIZE, dim, cd.gridM, cd.gridCoord);
-    if (g.G != cd.gridG) return 1 << 30;
-    std::vector<uint2> words = cd.gridWords.Download();
-    std::vector<int> cellStart = cd.gridCellStart.Download();
-    std::vector<unsigned short> idx = cd.gridIdx.Download();
-    int bad = 0, rank = 0;
-    const size_t cells = g.start.size() - 1;
-    for (size_t cell = 0; cell < cells; cell++) {
-        const uint2 w = words[cell >> 5];
-        const bool occupied = (w.x >> (cell & 31)) & 1u;
-        if ((cell & 31) == 0 && (int)w.y != rank) {  // the word's rank = non-empty cells before it
-            bad++;
-            rank = (int)w.y;
-        }
-        if (occupied != (g.start[cell + 1] > g.start[cell])) {
-            bad++;
-            if (occupied) rank++;
-            continue;
-        }
-        if (!occupied) continue;
-        const int s0 = cellStart[rank], s1 = cellStart[rank + 1];
-        rank++;
-        if (s1 - s0 != g.start[cell + 1] - g.start[cell]) {
-            bad++;
-            continue;
-        }
-        std::vector<std::vector<float>> dv, hv;  // the same set of rows (the device lists indices into the point table, in the order of its atomics)
-        for (int j = s0; j < s1; j++) dv.emplace_back(pts.begin() + (size_t)idx[j] * dim, pts.begin() + (size_t)(idx[j] + 1) * dim);
-        for (int j = g.start[cell]; j < g.start[cell + 1]; j++) hv.emplace_back(g.rows.begin() + (size_t)j * dim, g.rows.begin() + (size_t)(j + 1) * dim);
-        std::sort(dv.begin(), dv.end()), std::sort(hv.begin(), hv.end());
-        if (dv != hv) bad++;
-    }
-    return bad;
-    LMC_CATCH(-1)
-}
-
-// Host-only (no GPU): what the front end made of a scene file, as one JSON document -- the cross-check surface of the parsers (XML, .serialized,
-// OBJ, textures) against independent ones (tests/test_scene_io.py).  Returns the document's length (it is truncated to cap - 1 characters), -1 on error.
-long long lmc_scene_dump(const char *scene_xml, int force_diffuse, char *out, long long cap) {
-    LMC_TRY
-    lmc::LoadOverrides ov;
-    ov.forceDiffuse = force_diffuse != 0;
-    std::unique_ptr<lmc::Scene> sc = lmc::ParseScene(scene_xml, ov);
-    std::string j;
-    char buf[512];
-    auto num = [&](double v) {
-        snprintf(buf, sizeof(buf), "%.9g", v);
-        j += buf;
-    };
-    auto vec = [&](const float *v, int n) {
-        j += "[";
-        for (int k = 0; k < n; k++) {
-            if (k) j += ",";
-            num(v[k]);
-        }
-        j += "]";
-    };
-    auto tex = [&](const lmc::TextureRef &t) {
-        j += "{\"bitmap\":";
-        if (t.bitmap >= 0) {
-            const lmc::Bitmap &b = sc->bitmaps[t.bitmap];
-            std::string fn = b.filename;
-            const size_t slash = fn.find_last_of('/');
-            if (slash != std::string::npos) fn = fn.substr(slash + 1);
-            j += "\"" + fn + "\",\"width\":" + std::to_string(b.img.width) + ",\"height\":" + std::to_string(b.img.height) + ",\"gamma\":";
-            num(b.gamma);
-            j += ",\"average\":";
-            vec(b.avg, 3);
-        } else {
-            j += "null";
-        }
-        j += ",\"value\":";
-        vec(t.value, 3);
-        j += ",\"s_scale\":";
-        num(t.sScale);
-        j += ",\"t_scale\":";
-        num(t.tScale);
-        j += "}";
-    };
-    j += "{\"num_tris\":" + std::to_string(sc->numTris()) + ",\"meshes\":[";
-    for (size_t m = 0; m < sc->meshes.size(); m++) {
-        const lmc::Mesh &M = sc->meshes[m];
-        if (m) j += ",";
-        const float bmin[3] = {M.bmin.x, M.bmin.y, M.bmin.z}, bmax[3] = {M.bmax.x, M.bmax.y, M.bmax.z};
-        j += "{\"tris\":" + std::to_string(M.numTris()) + ",\"verts\":" + std::to_string(M.P.size()) + ",\"has_normals\":" + (M.N.empty() ? "false" : "true") + ",\"has_st\":" + (M.ST.empty() ? "false" : "true");
-        double area = 0;  // sum of the triangle areas, in double (Mesh::totalArea exists for emitters only)
-        for (size_t t = 0; t < M.numTris(); t++) {
-            const lmc::V3 &a = M.P[M.idx[3 * t]], &b = M.P[M.idx[3 * t + 1]], &c = M.P[M.idx[3 * t + 2]];
-            const double e1[3] = {(double)b.x - a.x, (double)b.y - a.y, (double)b.z - a.z}, e2[3] = {(double)c.x - a.x, (double)c.y - a.y, (double)c.z - a.z};
-            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-            area += 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);
-        }
-        j += ",\"material\":" + std::to_string(M.material) + ",\"area_light\":" + std::to_string(M.areaLight) + ",\"area\":";
-        num(area);
-        j += ",\"emitter_total_area\":";
-        num(M.totalArea);
-        j += ",\"bmin\":";
-        vec(bmin, 3);
-        j += ",\"bmax\":";
-        vec(bmax, 3);
-        j += "}";
-    }
-    j += "],\"materials\":[";
-    for (size_t m = 0; m < sc->materials.size(); m++) {
-        const lmc::Material &M = sc->materials[m];
-        if (m) j += ",";
-        j += "{\"type\":" + std::to_string(M.type) + ",\"two_sided\":" + (M.twoSided ? "true" : "false") + ",\"kd\":";
-        tex(M.Kd);
-        j += ",\"ks\":";
-        tex(M.Ks);
-        j += ",\"kt\":";
-        tex(M.Kt);
-        j += ",\"exp_or_alpha\":";
-        tex(M.expOrAlpha);
-        j += ",\"eta\":";
-        num(M.eta);
-        j += ",\"ks_weight\":";
-        num(M.KsWeight);
-        j += "}";
-    }
-    j += "],\"lights\":[";
-    for (size_t l = 0; l < sc->lights.size(); l++) {
-        const lmc::Light &L = sc->lights[l];
-        if (l) j += ",";
-        const float rad[3] = {L.radiance.x, L.radiance.y, L.radiance.z}, inten[3] = {L.intensity.x, L.intensity.y, L.intensity.z}, pos[3] = {L.position.x, L.position.y, L.position.z};
-        j += "{\"type\":" + std::to_string(L.type) + ",\"sampling_weight\":";
-        num(L.samplingWeight);
-        j += ",\"mesh\":" + std::to_string(L.mesh) + ",\"radiance\":";
-        vec(rad, 3);
-        j += ",\"intensity\":";
-        vec(inten, 3);
-        j += ",\"position\":";
-        vec(pos, 3);
-        j += ",\"env_width\":" + std::to_string(L.image.width) + ",\"env_height\":" + std::to_string(L.image.height) + ",\"env_normalization\":";
-        num(L.sampleInfo.normalization);
-        j += "}";
-    }
-    j += "],\"env_light\":" + std::to_string(sc->envLight) + ",\"light_cdf\":";
-    vec(sc->lightCdf.data(), (int)sc->lightCdf.size());
-    j += ",\"light_func_int\":";
-    num(sc->lightFuncInt);
-    const float c3[3] = {sc->bsphereCenter.x, sc->bsphereCenter.y, sc->bsphereCenter.z};
-    j += ",\"bsphere_center\":";
-    vec(c3, 3);
-    j += ",\"bsphere_radius\":";
-    num(sc->bsphereRadius);
-    const lmc::Camera &C = sc->camera;
-    j += ",\"camera\":{\"width\":" + std::to_string(C.width) + ",\"height\":" + std::to_string(C.height) + ",\"fov\":";
-    num(C.fov);
-    j += ",\"near\":";
-    num(C.nearClip);
-    j += ",\"far\":";
-    num(C.farClip);
-    const lmc::DptOptions &o = sc->options;
-    j += "},\"options\":{\"spp\":" + std::to_string(o.spp) + ",\"numinitsamples\":" + std::to_string(o.numInitSamples) + ",\"maxdepth\":" + std::to_string(o.maxDepth) + ",\"mindepth\":" + std::to_string(o.minDepth) +
-         ",\"directspp\":" + std::to_string(o.directSpp) + ",\"numchains\":" + std::to_string(o.numChains) + ",\"mala\":" + (o.mala ? "true" : "false") + ",\"h2mc\":" + (o.h2mc ? "true" : "false") + ",\"largestepprob\":";
-    num(o.largeStepProbability);
-    j += ",\"largestepscale\":";
-    num(o.largeStepProbScale);
-    j += ",\"perturbstddev\":";
-    num(o.perturbStdDev);
-    j += "},\"output\":\"" + sc->outputName + "\"}";
-    if (out && cap > 0) {
-        const size_t n = std::min<size_t>(j.size(), (size_t)cap - 1);
-        memcpy(out, j.data(), n);
-        out[n] = 0;
-    }
-    return (long long)j.size();
-    LMC_CATCH(-1)
-}
-
-// host-only probe of the existence test in front of the cache query (accel.cpp BuildCacheGrid + the kernel's candidate loop):
-// out[i] = 1 iff some cache point lies within the radius of query i.  No device needed.
-int lmc_cache_filter_probe(int dim, int npts, const float *pts, int nq, const float *q, int *out) {
-    LMC_TRY
-    if (dim < 3 || dim > MAXPSS) throw std::runtime_error("lmc_cache_filter_probe: bad dim");
-    bool first = true;
-    const int lead[4] = {0, 1, 2, 3};
-    for (int m = 3; m <= 4; m++)  // both grid ranks the kernel can be configured with ...
-        for (int chosen = 0; chosen < 2; chosen++) {  // ... over the leading coordinates and over the ones ChooseGridCoords picks: all must agree
-            lmc::CacheGrid g = lmc::BuildCacheGrid(pts, npts, dim, m, chosen ? nullptr : lead);
-            for (int i = 0; i < nq; i++) {
-                const int e = g.Exists(q + (size_t)i * dim, dim) ? 1 : 0;
-                if (!first && e != out[i]) throw std::runtime_error("lmc_cache_filter_probe: the grids disagree");
-                out[i] = e;
-            }
-            first = false;
-        }
-    return 0;
-    LMC_CATCH(-1)
-}
-// test probe (device/query_probe.hip): the lean small step's cache look-up on caller-given cache rows and chain states, next to the generic CacheQuery.
-// The kd-tree is the host build (as lmc_kd_probe's); the existence grid of rank grid_m lies over the leading coordinates or the ones ChooseGridCoords
-// picks, and is built by lmc::BuildCacheGrid on the host (converted to the compact layout) or by LaunchBuildCacheGrid on the device.
-int lmc_lean_query_probe(int dim, int npts, const float *pts, const float *v1, const float *v2, float malaStepsize, float malaStdDev, int gridM, int chosenCoords,
-                         int deviceGrid, int nq, const float *q, const int *queried, const float *lastPss, const float *chV1, const float *chV2, const float *ssScore,
-                         int *outInt, float *outW, float *outChain, float *outGauss, float *outGeneric) {
-    LMC_TRY
-    EnsureDevice(0);
-    if (dim < 6 || dim > PSS_MAX_LENGTH || (dim & 1) || npts < 1 || npts > PSS_MAX_SIZE || nq < 1 || gridM < 3 || gridM > 4)
-        throw std::runtime_error("lmc_lean_query_probe: bad arguments");
-    lmc::KdTreeResult t = lmc::BuildKdTree(pts, npts, dim);
-    if (t.depth >= KD_STACK || t.nodes.size() > KD_MAX_NODES) throw std::runtime_error("lmc_lean_query_probe: kd-tree deeper or larger than the search accepts");
-    DevBuf<KdNode> dN;
-    DevBuf<int> dV;
-    DevBuf<float> dP, dV1, dV2;
-    const size_t rowWords = (size_t)npts * dim;
-    dN.Upload(t.nodes), dV.Upload(t.vind), dP.Upload(pts, rowWords), dV1.Upload(v1, rowWords), dV2.Upload(v2, rowWords);
-    std::vector<DCache> cacheHost(1);
-    memset(cacheHost.data(), 0, sizeof(DCache));
-    DCacheDim &C = cacheHost[0].d[dim];
-    C.ready = 1, C.nodes = dN.p, C.vind = dV.p, C.pts = dP.p, C.v1 = dV1.p, C.v2 = dV2.p;
-    for (int k = 0; k < dim; k++) C.rootLow[k] = t.rootLow[k], C.rootHigh[k] = t.rootHigh[k];
-    // the existence grid
-    const int G = CacheGridG(dim), m = std::min(gridM, dim);
-    C.gridG = G, C.gridM = m;
-    for (int k = 0; k < 4; k++) C.gridCoord[k] = k;
-    if (chosenCoords) lmc::ChooseGridCoords(pts, npts, dim, m, C.gridCoord);
-    size_t cells = 1, nbrs = 1;
-    for (int k = 0; k < m; k++) cells *= G, nbrs *= 3;
-    const size_t nWords = (cells + 31) / 32;
-    DevBuf<uint2> dWords;
-    DevBuf<int> dCellStart, sStart, sCursor, sWordCount, sTiles;
-    DevBuf<unsigned short> dIdx;
-    if (deviceGrid) {
-        dWords.Alloc(nWords), dCellStart.Alloc(std::min(cells, (size_t)npts * nbrs) + 1), dIdx.Alloc((size_t)npts * nbrs);
-        sStart.Alloc(cells + 1), sCursor.Alloc(cells), sWordCount.Alloc(nWords), sTiles.Alloc((cells + 1) / 2048 + 2);
-        LaunchBuildCacheGrid(dP.p, npts, dim, G, m, C.gridCoord, sStart.p, sCursor.p, sWordCount.p, sTiles.p, dWords.p, dCellStart.p, dIdx.p, 0);
-        HIP_CHECK(hipGetLastError());
-    } else {
-        lmc::CacheGrid g = lmc::BuildCacheGrid(pts, npts, dim, m, C.gridCoord);
-        std::vector<uint2> words(nWords, uint2{0u, 0u});
-        std::vector<int> cellStart;
-        std::vector<unsigned short> idx(g.rowIdx.begin(), g.rowIdx.end());
-        for (size_t cell = 0; cell < cells; cell++) {
-            if ((cell & 31) == 0) words[cell >> 5].y = (unsigned)cellStart.size();
-            if (g.start[cell + 1] > g.start[cell]) words[cell >> 5].x |= 1u << (cell & 31), cellStart.push_back(g.start[cell]);
-        }
-        cellStart.push_back(g.start[cells]);
-        dWords.Upload(words), dCellStart.Upload(cellStart), dIdx.Upload(idx);
-    }
-    C.gridWords = dWords.p, C.gridCellStart = dCellStart.p, C.gridIdx = dIdx.p;
-    DevBuf<DCache> dCache;
-    dCache.Upload(cacheHost);
-    // the stand-in chain arrays ([word][chain], N = nq) and the queries
-    auto soa = [&](const float *rows) {
-        std::vector<float> v((size_t)dim * nq);
-        for (int i = 0; i < nq; i++)
-            for (int k = 0; k < dim; k++) v[(size_t)k * nq + i] = rows[(size_t)i * dim + k];
-        return v;
-    };
-    DevBuf<float> aV1, aV2, aLast, aWeight, dQ, dSs, oW, oGauss, oGeneric;
-    DevBuf<int> dQueried, oInt;
-    aV1.Upload(soa(chV1)), aV2.Upload(soa(chV2)), aLast.Upload(soa(lastPss)), aWeight.Alloc(nq);
-    dQ.Upload(q, (size_t)nq * dim), dSs.Upload(ssScore, nq), dQueried.Upload(queried, nq);
-    oInt.Alloc((size_t)nq * LEAN_PROBE_INTS), oW.Alloc((size_t)nq * 5), oGauss.Alloc((size_t)nq * (3 * dim + 1)), oGeneric.Alloc((size_t)nq * 2 * dim);
-    ChainArrays A;
-    memset(&A, 0, sizeof(A));
-    A.N = nq, A.chV1 = aV1.p, A.chV2 = aV2.p, A.chLastPss = aLast.p, A.pathWeight = aWeight.p;
-    std::vector<DScene> S(1);
-    memset(S.data(), 0, sizeof(DScene));
-    S[0].opt.malaStepsize = malaStepsize, S[0].opt.malaStdDev = malaStdDev;
-    StepParams P;
-    memset(&P, 0, sizeof(P));
-    LaunchLeanQueryProbe(S[0], dCache.p, A, P, dim, nq, dQ.p, dQueried.p, dSs.p, LeanQueryProbeOut{oInt.p, oW.p, oGauss.p, oGeneric.p}, 0);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(outInt, oInt.p, oInt.n * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(outW, oW.p, oW.n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(outGauss, oGauss.p, oGauss.n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(outGeneric, oGeneric.p, oGeneric.n * sizeof(float), hipMemcpyDeviceToHost));
-    const std::vector<float> after[3] = {aV1.Download(), aV2.Download(), aLast.Download()};
-    for (int i = 0; i < nq; i++)
-        for (int a = 0; a < 3; a++)
-            for (int k = 0; k < dim; k++) outChain[((size_t)i * 3 + a) * dim + k] = after[a][(size_t)k * nq + i];
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_gauss_probe(int n, int dim, const float *v1, const float *M, float ss, float shk, const float *sc, const float *offset, float *out) {
-    LMC_TRY
-    EnsureDevice(0);
-    DevBuf<float> dV, dM, dS, dO, dOut;
-    dV.Upload(v1, (size_t)n * dim), dM.Upload(M, (size_t)n * dim), dS.Upload(sc, n), dO.Upload(offset, (size_t)n * dim), dOut.Alloc((size_t)n * (3 * dim + 2));
-    LaunchGaussProbe(n, dim, dV.p, dM.p, ss, shk, dS.p, dO.p, dOut.p, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out, dOut.p, dOut.n * 4, hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// the H2MC step's cooperative launches on caller-supplied states (tests/test_gpu_h2mc.py)
-int lmc_h2_hess_probe(int c, int l, int n, const float *primary, const float *scene38, const float *vert, float *loglum, float *grad, float *hess) {
-    LMC_TRY
-    const int t = H2TechIndex(c, l);
-    if (t < 0) throw std::runtime_error("lmc_h2_hess_probe: technique (c,l) out of range");
-    EnsureDevice(0);
-    const int L = std::max(c + l - 1, 2), V = 238 + 59 * (c + l - 3), dim = 2 * L;
-    std::vector<float> rec((size_t)n * H2_REC_WORDS, 0.f);
-    for (int i = 0; i < n; i++) {
-        float *r = rec.data() + (size_t)i * H2_REC_WORDS;
-        memcpy(r, primary + (size_t)i * (2 * L + 1), (2 * L + 1) * sizeof(float));
-        memcpy(r + H2_REC_C, &c, 4), memcpy(r + H2_REC_L, &l, 4);
-        memcpy(r + H2_REC_VP, vert + (size_t)i * V, V * sizeof(float));
-    }
-    std::vector<int> items((size_t)n, 0), counts(2 * H2_COUNT_WORDS, 0);  // one bin holds everything: start (the second half of `counts`) is 0 everywhere
-    const int bin = t * H2_NSIG;
-    for (int i = 0; i < n; i++) items[i] = i;
-    counts[bin] = n;
-    DevBuf<float> dRec, dOut;
-    DevBuf<int> dItems, dCounts;
-    dRec.Upload(rec.data(), rec.size()), dItems.Upload(items.data(), items.size()), dCounts.Upload(counts.data(), counts.size()), dOut.Alloc((size_t)n * H2_OUT_WORDS);
-    LaunchH2Hess(dRec.p, H2Bins{dItems.p, dCounts.p, dCounts.p + H2_COUNT_WORDS, nullptr, nullptr}, n, scene38, dOut.p, 1024, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    const std::vector<float> o = dOut.Download();
-    for (int i = 0; i < n; i++) {
-        const float *r = o.data() + (size_t)i * H2_OUT_WORDS;
-        if (loglum) loglum[i] = r[H2_OUT_LOGLUM];
-        if (grad) memcpy(grad + (size_t)i * 16, r, 16 * sizeof(float));
-        if (hess) {
-            float *h = hess + (size_t)i * 256;
-            memset(h, 0, 256 * sizeof(float));
-            for (int a = 0; a < dim; a++)
-                for (int b = a; b < dim; b++) h[a * dim + b] = r[H2_OUT_HESS + a * dim + b];
-        }
-    }
-    return 0;
-    LMC_CATCH(-1)
-}
-int lmc_h2_gauss_probe(int n, int dim, const float *grad, const float *hess, float sigma, const float *offset, float *gauss, float *px) {
-    LMC_TRY
-    if (dim < 4 || dim > 16 || (dim & 1)) throw std::runtime_error("lmc_h2_gauss_probe: dim must be even, 4..16");
-    const int t = H2TechIndex(dim / 2 + 1, 0);
-    EnsureDevice(0);
-    std::vector<float> out((size_t)n * H2_OUT_WORDS, 0.f), off((size_t)MAXPSS * n, 0.f);
-    for (int i = 0; i < n; i++) {
-        memcpy(out.data() + (size_t)i * H2_OUT_WORDS, grad + (size_t)i * 16, 16 * sizeof(float));
-        memcpy(out.data() + (size_t)i * H2_OUT_WORDS + H2_OUT_HESS, hess + (size_t)i * dim * dim, (size_t)dim * dim * sizeof(float));
-        if (offset)
-            for (int k = 0; k < dim; k++) off[(size_t)k * n + i] = offset[(size_t)i * dim + k];
-    }
-    std::vector<int> items((size_t)n, 0), counts(2 * H2_COUNT_WORDS, 0);  // one bin holds everything: start (the second half of `counts`) is 0 everywhere
-    const int bin = t * H2_NSIG;
-    for (int i = 0; i < n; i++) items[i] = i;
-    counts[bin] = n;
-    DevBuf<float> dOut, dOff, dGauss, dPx;
-    DevBuf<int> dItems, dCounts, dFlags;
-    dOut.Upload(out.data(), out.size()), dOff.Upload(off.data(), off.size()), dItems.Upload(items.data(), items.size()), dCounts.Upload(counts.data(), counts.size());
-    dGauss.Alloc(2 * (size_t)n * H2_GAUSS_AOS), dPx.Alloc(n), dFlags.Alloc(n);
-    LaunchH2Gauss(H2Bins{dItems.p, dCounts.p, dCounts.p + H2_COUNT_WORDS, nullptr, nullptr}, n, dOut.p, lmcd::MakeH2MCParam(sigma), 0, dFlags.p, 1, dGauss.p, dOff.p, dPx.p, 256, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (gauss) HIP_CHECK(hipMemcpy(gauss, dGauss.p + (size_t)n * H2_GAUSS_AOS, (size_t)n * H2_GAUSS_AOS * sizeof(float), hipMemcpyDeviceToHost));  // stage 1 with F_GSEL clear: the second buffer
-    if (px) HIP_CHECK(hipMemcpy(px, dPx.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-    LMC_CATCH(-1)
-}
-
-// ---- the reference's plugin symbols (pathlibbidir_mala.so): 42 forward + 42 derivative programs.
-// A single evaluation is one (tiny) kernel launch; throughput users call lmc_grad_batch.
-// Per calling thread: a stream and two host-mapped pinned buffers, created on the first call and kept.  A call copies the caller's
-// arrays into the input buffer (a few hundred floats, host memcpy), launches ONE single-wave kernel that reads them over the bus and
-// writes the result into the output buffer, and waits for the stream: no allocation, no copy call, no device-wide sync (round 2:
-// five hipMalloc + three H2D + hipDeviceSynchronize + two D2H per call, 100-200 us).  Re-entrant like the reference's symbols
-// (mutation_mala.h:97-110 calls them from every worker thread with thread-private buffers): nothing is shared between threads.
-extern "C++" {
-namespace {
-struct PluginSlot {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    float *hostIn = nullptr, *hostOut = nullptr, *devIn = nullptr, *devOut = nullptr, *devStage = nullptr;
-    void Ensure() {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (stream && dev == device) return;
-        Release();
-        EnsureDevice(dev);
-        device = dev;
-        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        HIP_CHECK(hipHostMalloc((void **)&hostIn, (17 + 38 + 600) * sizeof(float), hipHostMallocMapped));
-        HIP_CHECK(hipHostMalloc((void **)&hostOut, (1 + 16 + 256) * sizeof(float), hipHostMallocMapped));
-        HIP_CHECK(hipHostGetDevicePointer((void **)&devIn, hostIn, 0));
-        HIP_CHECK(hipHostGetDevicePointer((void **)&devOut, hostOut, 0));
-        HIP_CHECK(hipMalloc((void **)&devStage, (17 + 38 + 600) * sizeof(float)));
-    }
-    void Release() {
-        if (hostIn) (void)hipHostFree(hostIn);
-        if (hostOut) (void)hipHostFree(hostOut);
-        if (devStage) (void)hipFree(devStage);
-        if (stream) (void)hipStreamDestroy(stream);
-        hostIn = hostOut = devIn = devOut = devStage = nullptr, stream = nullptr, device = -1;
-    }
-    ~PluginSlot() { Release(); }
-};
-thread_local PluginSlot g_pluginSlot;
-
-// returns false (after printing why) when the evaluation could not run: the outputs are NaN then, the reference's own failure convention
-bool PluginCall(int c, int l, const float *primary, const float *scene, const float *vertParams, int mode /* 0 value, 1 gradient, 2 Hessian */) {
-    try {
-        if (!(c >= 1 && l >= 0 && c + l >= 3 && c + l - 1 <= 8)) throw std::runtime_error("technique (c,l) out of range");
-        PluginSlot &P = g_pluginSlot;
-        P.Ensure();
-        const int L = std::max(c + l - 1, 2), V = 238 + 59 * (c + l - 3);
-        memcpy(P.hostIn, primary, (size_t)(2 * L + 1) * sizeof(float));
-        memcpy(P.hostIn + 17, scene, 38 * sizeof(float));
-        memcpy(P.hostIn + 55, vertParams, (size_t)V * sizeof(float));
-        if (mode == 2) LaunchPluginHess(c, l, P.devIn, P.devStage, P.devOut, P.stream);
-        else
-            LaunchPluginGrad(c, l, P.devIn, P.devOut, mode, P.stream);
-        HIP_CHECK(hipStreamSynchronize(P.stream));
-        return true;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        fprintf(stderr, "lmc: path program (%d,%d) failed: %s\n", c, l, e.what());
-        return false;
-    }
-}
-}  // namespace
-}  // extern "C++"
-static void PluginEval(int c, int l, const float *primary, const float *scene, const float *vertParams, float *logLum, float *grad) {
-    const int L = std::max(c + l - 1, 2);
-    const bool ok = PluginCall(c, l, primary, scene, vertParams, grad ? 1 : 0);
-    const float *o = g_pluginSlot.hostOut;
-    if (logLum) logLum[0] = ok ? o[0] : NAN;
-    if (grad)
-        for (int k = 0; k < 2 * L; k++) grad[k] = ok ? o[1 + k] : NAN;
-}
-static void PluginEvalHess(int c, int l, const float *primary, const float *scene, const float *vertParams, float *grad, float *hess) {
-    const int L = std::max(c + l - 1, 2), dim = 2 * L;
-    const bool ok = PluginCall(c, l, primary, scene, vertParams, 2);
-    const float *o = g_pluginSlot.hostOut;
-    if (grad)
-        for (int k = 0; k < dim; k++) grad[k] = ok ? o[1 + k] : NAN;
-    if (hess)
-        for (int k = 0; k < dim * dim; k++) hess[k] = ok ? o[17 + k] : NAN;
-}
-#define LMC_PLUGIN(C, Lg)                                                                                                                          \
-    void evaluate_path_bidir_mala_##C##_##Lg##_static(const float *, const float *primary, const float *scene, const float *vp, float *logLum) {   \
-        PluginEval(C, Lg, primary, scene, vp, logLum, nullptr);                                                                                    \
-    }                                                                                                                                              \
-    void evaluate_path_bidir_mala_##C##_##Lg##_static_derv(const float *, const float *primary, const float *scene, const float *vp, float *grad) { \
-        PluginEval(C, Lg, primary, scene, vp, nullptr, grad);                                                                                      \
-    }                                                                                                                                              \
-    /* H2MC library (pathlibbidir.so, chad.cpp:884-895; caller mutation_h2mc.h:74-79): same forward program, derivative with Hessian */          \
-    void evaluate_path_bidir_##C##_##Lg##_static(const float *, const float *primary, const float *scene, const float *vp, float *logLum) {        \
-        PluginEval(C, Lg, primary, scene, vp, logLum, nullptr);                                                                                    \
-    }                                                                                                                                              \
-    void evaluate_path_bidir_##C##_##Lg##_static_derv(const float *, const float *primary, const float *scene, const float *vp, float *grad, float *hess) { \
-        PluginEvalHess(C, Lg, primary, scene, vp, grad, hess);                                                                                     \
-    }
-// (c,l) with 1<=c<=9, 0<=l<=8, 3<=c+l<=9 (path.cpp:3955-3959)
-LMC_PLUGIN(1, 2) LMC_PLUGIN(1, 3) LMC_PLUGIN(1, 4) LMC_PLUGIN(1, 5) LMC_PLUGIN(1, 6) LMC_PLUGIN(1, 7) LMC_PLUGIN(1, 8)
-LMC_PLUGIN(2, 1) LMC_PLUGIN(2, 2) LMC_PLUGIN(2, 3) LMC_PLUGIN(2, 4) LMC_PLUGIN(2, 5) LMC_PLUGIN(2, 6) LMC_PLUGIN(2, 7)
-LMC_PLUGIN(3, 0) LMC_PLUGIN(3, 1) LMC_PLUGIN(3, 2) LMC_PLUGIN(3, 3) LMC_PLUGIN(3, 4) LMC_PLUGIN(3, 5) LMC_PLUGIN(3, 6)
-LMC_PLUGIN(4, 0) LMC_PLUGIN(4, 1) LMC_PLUGIN(4, 2) LMC_PLUGIN(4, 3) LMC_PLUGIN(4, 4) LMC_PLUGIN(4, 5)
-LMC_PLUGIN(5, 0) LMC_PLUGIN(5, 1) LMC_PLUGIN(5, 2) LMC_PLUGIN(5, 3) LMC_PLUGIN(5, 4)
-LMC_PLUGIN(6, 0) LMC_PLUGIN(6, 1) LMC_PLUGIN(6, 2) LMC_PLUGIN(6, 3)
-LMC_PLUGIN(7, 0) LMC_PLUGIN(7, 1) LMC_PLUGIN(7, 2)
-LMC_PLUGIN(8, 0) LMC_PLUGIN(8, 1)
-LMC_PLUGIN(9, 0)
 
 }  // extern "C"

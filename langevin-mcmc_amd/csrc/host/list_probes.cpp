@@ -15,7 +15,7 @@
 #include "../../../include/lmc_abi.h"
 #include "../device/kernels.h"
 #include "../device/dh2coop.h"
-#include "last_error.h"
+#include "hostutil.h"
 
 using namespace lmcd;
 
@@ -23,23 +23,10 @@ static_assert(LMC_PROBE_BINS == H2_NBINS, "include/lmc_abi.h: LMC_PROBE_BINS is 
 static_assert(LMC_PROBE_CACHE_ROWS == PSS_MAX_SIZE, "include/lmc_abi.h: LMC_PROBE_CACHE_ROWS is the row count of a cache dim");
 static_assert(PSS_MAX_LENGTH == 12 && CACHE_SLOTS == 4, "lmc_cache_push_probe lays its rows out for the dims 6, 8, 10, 12");
 
-#define HIP_CHECK(x)                                                                                                  \
-    do {                                                                                                              \
-        hipError_t e_ = (x);                                                                                          \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
-    } while (0)
-#define PROBE_TRY try {
-#define PROBE_CATCH                   \
-    }                                 \
-    catch (const std::exception &e) { \
-        LmcSetLastError(e.what());    \
-        return -1;                    \
-    }
-
 namespace {
 
 template <class T>
-struct Buf {  // device array of at least one element
+struct Buf {  // device array of at least one element (unlike hostutil.h's DevBuf never a null pointer, and it has Fill)
     T *p = nullptr;
     size_t n = 0;
     Buf() {}
@@ -95,7 +82,7 @@ constexpr int kSentinel = LMC_PROBE_SENTINEL;
 extern "C" {
 
 int lmc_scan_probe(int n, const int *in, int *out) {
-    PROBE_TRY
+    LMC_TRY
     Require(n >= 1 && in && out, "lmc_scan_probe: n >= 1 and both arrays are required");
     Stream st;
     Buf<int> v, sums;
@@ -104,11 +91,11 @@ int lmc_scan_probe(int n, const int *in, int *out) {
     st.Finish();
     v.Download(out, n);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_radix_sort_probe(int n, int n_max, const unsigned *keys, int *out_vals, unsigned *out_keys) {
-    PROBE_TRY
+    LMC_TRY
     Require(n_max >= 1 && n >= 0 && n <= n_max && keys && out_vals && out_keys, "lmc_radix_sort_probe: 0 <= n <= n_max, n_max >= 1 and all arrays are required");
     Stream st;
     const size_t nb = RelocSortBlocks(n_max);
@@ -123,11 +110,11 @@ int lmc_radix_sort_probe(int n, int n_max, const unsigned *keys, int *out_vals, 
     st.Finish();
     outV.Download(out_vals, n_max), k1.Download(out_keys, n_max);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_sort_by_technique_probe(int n_chains, const unsigned char *next_kind, int n_list, const int *list, int max_entries, int *out) {
-    PROBE_TRY
+    LMC_TRY
     Require(n_chains >= 1 && next_kind && n_list >= 0 && max_entries >= n_list && (n_list == 0 || (list && out)), "lmc_sort_by_technique_probe: bad arguments");
     for (int i = 0; i < n_list; i++) Require(list[i] >= 0 && list[i] < n_chains, "lmc_sort_by_technique_probe: list entry out of range");
     Stream st;
@@ -141,12 +128,12 @@ int lmc_sort_by_technique_probe(int n_chains, const unsigned char *next_kind, in
     for (int i = n_list; i < max_entries; i++) Require(all[i] == kSentinel, "lmc_sort_by_technique_probe: the launch wrote beyond the list's count");
     if (n_list) memcpy(out, all.data(), (size_t)n_list * sizeof(int));
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_build_lists_probe(int N, const unsigned char *next_kind, int sort_plain, unsigned lean_dims, int want_step_kind, int *out_large, int *out_generic,
                           int *out_plain, int *out_counts, unsigned char *out_step_kind) {
-    PROBE_TRY
+    LMC_TRY
     Require(N >= 1 && next_kind && sort_plain >= 0 && sort_plain <= 3 && out_large && out_generic && out_plain && out_counts && (!want_step_kind || out_step_kind),
             "lmc_build_lists_probe: bad arguments");
     Stream st;
@@ -162,11 +149,11 @@ int lmc_build_lists_probe(int N, const unsigned char *next_kind, int sort_plain,
     large.Download(out_large, N), generic.Download(out_generic, N), plain.Download(out_plain, N), counts.Download(out_counts, 3);
     if (want_step_kind) sk.Download(out_step_kind, N);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_bins_compact_probe(int N, const int *bin_of, const int *count, int n_list, const int *list, int grid_blocks, int *out_items, int *out_start) {
-    PROBE_TRY
+    LMC_TRY
     Require(N >= 1 && bin_of && count && n_list >= 0 && n_list <= N && (n_list == 0 || list) && grid_blocks >= 1 && grid_blocks <= 65536 && out_items && out_start,
             "lmc_bins_compact_probe: bad arguments");
     // the scatter trusts the counts: they must be the list's own
@@ -186,11 +173,11 @@ int lmc_bins_compact_probe(int N, const int *bin_of, const int *count, int n_lis
     st.Finish();
     items.Download(out_items, N), start.Download(out_start, H2_NBINS);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_split_list_probe(int n_list, const int *list, int parts, int stride, int grid_blocks, int *out_sub, int *out_sub_count) {
-    PROBE_TRY
+    LMC_TRY
     Require(n_list >= 0 && (n_list == 0 || list) && parts >= 1 && parts <= 4 && grid_blocks >= 1 && grid_blocks <= 65536 && out_sub && out_sub_count,
             "lmc_split_list_probe: bad arguments");
     const int groups = (n_list + 63) / 64;  // a part receives at most ceil(groups / parts) groups of 64
@@ -202,12 +189,12 @@ int lmc_split_list_probe(int n_list, const int *list, int parts, int stride, int
     st.Finish();
     sub.Download(out_sub, (size_t)parts * stride), subCount.Download(out_sub_count, parts);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_cache_push_probe(int N, const int *push_dim, const float *push_data, const int *slot_of, const int *initial_counts, float *out_rows, float *out_weights,
                          int *out_counts, int *out_push_dim) {
-    PROBE_TRY
+    LMC_TRY
     Require(N >= 1 && push_dim && push_data && initial_counts && out_rows && out_weights && out_counts && out_push_dim, "lmc_cache_push_probe: bad arguments");
     for (int sl = 0; sl < CACHE_SLOTS; sl++) Require(initial_counts[sl] >= 0 && initial_counts[sl] <= PSS_MAX_SIZE, "lmc_cache_push_probe: initial count out of range");
     if (slot_of) {
@@ -262,12 +249,12 @@ int lmc_cache_push_probe(int N, const int *push_dim, const float *push_data, con
     }
     dCount.Download(out_counts, CACHE_SLOTS), dDim.Download(out_push_dim, N);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 int lmc_reloc_plan_probe(int N, const unsigned char *step_kind, const int *c, const int *l, const int *flags, const unsigned *placed_key, int without_gaussian_only,
                          int capacity, int skipped_before, int *out_count, int *out_members, int *out_sorted) {
-    PROBE_TRY
+    LMC_TRY
     Require(N >= 1 && step_kind && c && l && flags && placed_key && capacity >= 0 && out_count && out_members && out_sorted, "lmc_reloc_plan_probe: bad arguments");
     std::vector<float> contrib((size_t)2 * N);  // words 0 and 1 of A.curContrib: camera and light depth, as integers
     memcpy(contrib.data(), c, (size_t)N * 4), memcpy(contrib.data() + N, l, (size_t)N * 4);
@@ -288,7 +275,7 @@ int lmc_reloc_plan_probe(int N, const unsigned char *step_kind, const int *c, co
     st.Finish();
     count.Download(out_count, 2), members.Download(out_members, N), sorted.Download(out_sorted, N);
     return 0;
-    PROBE_CATCH
+    LMC_CATCH(-1)
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Host-side bookkeeping of the exact mc film (lmc_mc_accumulate / lmc_mc_coverage / lmc_mc_save / lmc_mc_load; INTEGRATION.md "Exact mc film"):
 // which stream ids of [0, nTiles * spp) a film holds, how a call's range is cut into launches, and the state file.
-// Pure C++ (no HIP): context.cpp calls these around its launches, and the CPU tier reaches them through lmc_mc_file_info and the
+// Pure C++ (no HIP): mcrender.cpp calls these around its launches, and the CPU tier reaches them through lmc_mc_file_info and the
 // lmc_mc_coverage_probe / lmc_mc_chunks_probe hooks (tests/test_mc_exact_abi.py, tests/helpers/mcfilm_main.cpp).
 #pragma once
 #include <cstdint>

@@ -725,7 +725,7 @@ def test_deterministic_trigonometry_and_logf_bit_equal_on_device():
 
 def test_plugin_symbol_call_cost_and_threads(pair_full):
     """the drop-in symbols must not cost 100-200 us per call.  Each calling thread owns a stream and two
-    host-mapped pinned buffers (context.cpp PluginSlot); a call = host memcpy of the arguments + ONE single-wave launch + one
+    host-mapped pinned buffers (plugin_abi.cpp PluginSlot); a call = host memcpy of the arguments + ONE single-wave launch + one
     stream sync.  Asserted: mean < 60 us over 1000 gradient calls on full-material states (measured ~ 35 us), the single call
     equals the batched kernel, the H2MC symbol equals lmc_hess_batch, and four threads calling concurrently (the reference calls
     the symbols from every worker thread, mutation_mala.h:97-110) get their own results."""

@@ -24,6 +24,11 @@ def _product_lib():
     return ctypes.CDLL(p.LIB_PATH)
 
 
+def plugin_techniques():
+    """the (c, l) of the reference's plugin symbols (path.cpp:3955-3959)"""
+    return [(c, l) for c in range(1, 10) for l in range(0, 9) if 3 <= c + l <= 9]
+
+
 def test_abi_exports_every_declared_symbol():
     lib = _product_lib()
     hdr = open(os.path.join(ROOT, "include", "lmc_abi.h")).read()
@@ -34,12 +39,10 @@ def test_abi_exports_every_declared_symbol():
         assert hasattr(lib, n), "missing export " + n
     # the reference's plugin symbols: 42 forward + 42 derivative programs (path.cpp:3955-3959)
     cnt = 0
-    for c in range(1, 10):
-        for l in range(0, 9):
-            if 3 <= c + l <= 9:
-                for suffix in ("static", "static_derv"):
-                    assert hasattr(lib, "evaluate_path_bidir_mala_%d_%d_%s" % (c, l, suffix))
-                    cnt += 1
+    for c, l in plugin_techniques():
+        for suffix in ("static", "static_derv"):
+            assert hasattr(lib, "evaluate_path_bidir_mala_%d_%d_%s" % (c, l, suffix))
+            cnt += 1
     assert cnt == 84
 
 
