@@ -193,6 +193,30 @@ int lmc_group_mc_accumulate(lmc_ctx **ctxs, int n, int spp, long long stream_beg
 int lmc_mc_save(lmc_ctx *ctx, const char *path);
 int lmc_mc_load(lmc_ctx *ctx, const char *path);
 long long lmc_mc_file_info(const char *path, char *json, long long cap);
+/* Layered mc film (INTEGRATION.md "Layered mc film"): lmc_set_option "mc_layers" = 1 (by path length) or 2 (by technique), default 0 (off: the film and the
+ * kernels above), takes effect at the next lmc_mc_render and, in either film mode and with either generator, renders the same streams into one film
+ * per layer; the split happens where a contribution is added, so the layers of one render sum to its unlayered film -- in exact mode word for word.
+ *   numbering    D = the context's maxdepth (1 .. 12), a contribution's technique (c, l) = (camDepth, lightDepth) of SubpathContrib, L = c + l - 1 its length.
+ *                "mc_layers" = 1: D layers, layer L - 1 holds length L = 1 .. D.
+ *                "mc_layers" = 2: D (D + 3) / 2 layers, for L = 1 .. D and l = 0 .. L (c = L + 1 - l) layer (L - 1)(L + 2) / 2 + l: 27 layers at D = 6, 44 at 8.
+ *                Layers a generator or a mindepth never reaches stay zero.  A contribution outside the table cannot occur; it would be dropped (exact mode: and
+ *                counted by lmc_mc_overflow), never written.
+ *   storage      n_layers * W*H*3 words on the device (exact mode: int64, and one overflow word); an allocation failure names the byte count and "mc_layers"
+ *   per layer    the luminance, finite and range rules, the 1 / spp weight of float mode and the counters are those of the unlayered film, per contribution;
+ *                stream ranges, "mc_launch_streams" cuts and, in exact mode, lmc_mc_accumulate work as above.  lmc_mc_accumulate with "mc_layers" set to
+ *                another value than the film was rendered with returns -1 and leaves the film as it was.
+ *   the total    lmc_mc_read, lmc_mc_read_fixed, lmc_mc_overflow, lmc_mc_stats and lmc_mc_coverage apply to the sum of the layers (int64 adds; float mode:
+ *                float adds in increasing layer index): a caller that ignores the layers sees the unlayered image, in exact mode the same words
+ *   lmc_mc_layer_info        *mode, *n_layers of the film the context holds (n_layers = 0: unlayered); cl receives at most cap pairs, (L, -1) in length
+ *                            mode, (c, l) in technique mode
+ *   lmc_mc_read_layer        one layer as W*H*3 floats; exact mode: float((double)q * 2^-32 / (double)spp) like lmc_mc_read
+ *   lmc_mc_read_layer_fixed  one layer's raw words; -1 in float mode.  A layer index outside [0, n_layers) returns -1.
+ * Limits of this version: the mc integrator only (the MLT film is not layered); no state file and no group -- lmc_mc_save of a layered film, lmc_mc_load into
+ * a context set to "mc_layers", lmc_group_mc_render and lmc_group_mc_accumulate with such a member return -1 naming mc_layers, render and write nothing, and
+ * leave the contexts usable. */
+int lmc_mc_layer_info(lmc_ctx *ctx, int *mode, int *n_layers, int *cl, int cap);
+int lmc_mc_read_layer(lmc_ctx *ctx, int layer, float *rgb);
+int lmc_mc_read_layer_fixed(lmc_ctx *ctx, int layer, long long *words);
 /* test hooks of the host-side bookkeeping (host/mcfilm.cpp), host only.  coverage_probe: the n_adds ranges adds[2 i], adds[2 i + 1] are added in turn to an
  * empty coverage, accepted[i] = 1 / 0; cov / comp receive the ranges then held / what [0, total) lacks (at most their cap pairs; *n_cov / *n_comp the full
  * numbers).  chunks_probe: the launches a call over [begin, end) is cut into; returns their number, writes at most cap pairs. */

@@ -91,6 +91,10 @@ def lib():
             L.lmc_mc_file_info.restype = c_ll
             L.lmc_mc_coverage_probe.argtypes = [vp, ctypes.c_int, c_ll, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp]
             L.lmc_mc_chunks_probe.argtypes = [c_ll, c_ll, c_ll, c_ll, vp, ctypes.c_int]
+        if hasattr(L, "lmc_mc_layer_info"):  # (an A/B library built from an older tree, LMC_LIB, has no layered mc film)
+            L.lmc_mc_layer_info.argtypes = [vp, vp, vp, vp, ctypes.c_int]
+            L.lmc_mc_read_layer.argtypes = [vp, ctypes.c_int, vp]
+            L.lmc_mc_read_layer_fixed.argtypes = [vp, ctypes.c_int, vp]
         L.lmc_stream_probe.argtypes = [c_ll, ctypes.c_int]
         L.lmc_grad_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
         L.lmc_trace.argtypes = [vp, ctypes.c_int, vp, vp, vp]
@@ -363,6 +367,46 @@ class Renderer:
         generator raises naming the field and leaves the context as it was.  mc_accumulate then continues the render."""
         if lib().lmc_mc_load(self.h, os.fsencode(path)) != 0:
             raise RuntimeError("lmc_mc_load failed: " + _err())
+
+    # ---- the layered mc film (set_option("mc_layers", 1 | 2) before mc_render; include/lmc_abi.h "Layered mc film")
+    def mc_layer_info(self):
+        """(mode, layers) of the mc film the renderer holds: mode 0 / 1 (by path length) / 2 (by technique), layers a list of (L, -1) in length
+        mode and of (camDepth, lightDepth) in technique mode, [] for an unlayered film"""
+        mode, n = ctypes.c_int(), ctypes.c_int()
+        if lib().lmc_mc_layer_info(self.h, ctypes.byref(mode), ctypes.byref(n), None, 0) != 0:
+            raise RuntimeError(_err())
+        cl = (ctypes.c_int * (2 * max(n.value, 1)))()
+        if lib().lmc_mc_layer_info(self.h, ctypes.byref(mode), ctypes.byref(n), cl, n.value) != 0:
+            raise RuntimeError(_err())
+        return mode.value, [(int(cl[2 * k]), int(cl[2 * k + 1])) for k in range(n.value)]
+
+    def mc_layer(self, k):
+        """layer k of the layered mc film as mc_film() returns the whole, float32 [H, W, 3]"""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        if lib().lmc_mc_read_layer(self.h, int(k), P(out)) != 0:
+            raise RuntimeError("lmc_mc_read_layer failed: " + _err())
+        return out
+
+    def mc_layer_fixed(self, k):
+        """layer k's raw words, int64 [H, W, 3]; raises in float mode"""
+        f = np.zeros((self.height, self.width, 3), np.int64)
+        if lib().lmc_mc_read_layer_fixed(self.h, int(k), P(f)) != 0:
+            raise RuntimeError("lmc_mc_read_layer_fixed failed: " + _err())
+        return f
+
+    def mc_layers(self):
+        """every layer, float32 [n, H, W, 3]; in float mode mc_film() is their float sum in layer order"""
+        n = len(self.mc_layer_info()[1])
+        if n == 0:
+            raise RuntimeError("mc_layers: the renderer holds no layered mc film (set_option(\"mc_layers\", 1 or 2) before mc_render)")
+        return np.stack([self.mc_layer(k) for k in range(n)])
+
+    def mc_layers_fixed(self):
+        """every layer's raw words, int64 [n, H, W, 3]; their sum over the first axis is mc_film_fixed()"""
+        n = len(self.mc_layer_info()[1])
+        if n == 0:
+            raise RuntimeError("mc_layers_fixed: the renderer holds no layered mc film (set_option(\"mc_layers\", 1 or 2) before mc_render)")
+        return np.stack([self.mc_layer_fixed(k) for k in range(n)])
 
     def stats(self):
         s = (c_ll * 8)()

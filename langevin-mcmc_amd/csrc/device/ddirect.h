@@ -4,6 +4,9 @@
 // DirectLighting :195-294, BSDFSampling :296-386, RussianRoulette :388-404 (lens* / jacobian terms feed nothing here).
 // The image the reference writes is direct / directSpp + indirect / spp (mlt.cpp:203-207).
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "dpath.h"
 
 namespace lmcd {
@@ -31,6 +34,19 @@ struct LaneSink {
         n++;
     }
 };
+
+// A sink that splits its film by technique (mc.hip, the layered mc film) declares Technique(screenPos, contrib, camDepth, lightDepth) and is handed
+// SubpathContrib's labels (2 + camDepth, 0 | 1; path.cpp GeneratePath); every other sink sees the plain call, and nothing of this is compiled into it
+template <class Sink, class = void>
+struct SinkTakesTechnique : std::false_type {};
+template <class Sink>
+struct SinkTakesTechnique<Sink, std::void_t<decltype(std::declval<Sink &>().Technique(V2{}, V3{}, 0, 0))>> : std::true_type {};
+template <class Sink>
+LMC_D void EmitContrib(Sink &sink, V2 screenPos, V3 contrib, int camDepth, int lightDepth) {
+    if constexpr (SinkTakesTechnique<Sink>::value) sink.Technique(screenPos, contrib, 2 + camDepth, lightDepth);
+    else
+        sink(screenPos, contrib);
+}
 
 // pcg32_k64 read-only: a lane that evaluates a sample ahead of the committed stream position must not advance the stream's
 // extension table; it reports the case instead (`crossed`, once per 2^32 draws) and counts its draws
@@ -108,7 +124,7 @@ LMC_D void DirectSample(const DScene &S, Sink &sink, int px, int py, int minDept
                     const float lightPickProb = PickLightProb(S, light);
                     contrib = contrib * MISWeight(lastBsdfPdf, directPdf * lightPickProb);
                 }
-                if (Luminance(contrib) > 0.0f) sink(screenPos, contrib);
+                if (Luminance(contrib) > 0.0f) EmitContrib(sink, screenPos, contrib, camDepth, 0);
             }
             return;
         }
@@ -132,7 +148,7 @@ LMC_D void DirectSample(const DScene &S, Sink &sink, int px, int py, int minDept
                     V3 contrib = cmul(throughput, bsdfContrib);
                     contrib = cmul(contrib, lightContrib) * inverse(lightPickProb);
                     if (!LightIsDelta(S, dl)) contrib = contrib * MISWeight(directPdf * lightPickProb, bsdfPdf);
-                    if (Luminance(contrib) > 0.0f) sink(screenPos, contrib);
+                    if (Luminance(contrib) > 0.0f) EmitContrib(sink, screenPos, contrib, camDepth, 1);
                 }
             }
         }

@@ -62,8 +62,21 @@ void LaunchBidirMC(const lmcd::DScene &S, const lmcd::Film &film, int nThreads, 
 // the mc integrator (mc.hip): stream ids [streamBegin, streamEnd) of nTiles * spp; tabScratch: 64 words per thread (MCThreads), counters: 2 x u64
 // film: float (contributions weighted by 1 / spp) or, with FILM_EXACT in its H (FilmFx), W*H*3 + 1 fixed-point words of unweighted contributions, the last
 // the overflow counter; the launch adds to the film and to the counters, it clears neither
-void LaunchMC(const lmcd::DScene &S, const lmcd::Film &film, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin, long long streamEnd,
-              uint32_t *tabScratch, unsigned long long *counters, hipStream_t s);
+// layerMode ("mc_layers"): 0: the film as above; 1 / 2: nLayers films one after the other (exact: one overflow word behind the last), a contribution in the
+// layer McLayerOf gives its (camDepth, lightDepth)
+void LaunchMC(const lmcd::DScene &S, const lmcd::Film &film, int layerMode, int nLayers, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin,
+              long long streamEnd, uint32_t *tabScratch, unsigned long long *counters, hipStream_t s);
+// The layer of technique (c, l) = (camDepth, lightDepth), path length L = c + l - 1 >= 1.  Mode 1 (by length): L - 1.  Mode 2 (by technique): the
+// lengths one after the other, length L with its L + 1 techniques l = 0 .. L: (L - 1)(L + 2) / 2 + l.  -1: no such technique.  With D = maxdepth a
+// film has McLayerCount layers, and a technique belongs to the table when its layer is below that.
+LMC_HD int McLayerOf(int mode, int c, int l) {
+    const int L = c + l - 1;
+    if (c < 1 || l < 0 || L < 1) return -1;
+    return mode == 1 ? L - 1 : (L - 1) * (L + 2) / 2 + l;
+}
+LMC_HD int McLayerCount(int mode, int maxDepth) { return mode == 1 ? maxDepth : mode == 2 ? maxDepth * (maxDepth + 3) / 2 : 0; }
+void LaunchMCSumLayers(const long long *layers, long long *total, size_t n, int nLayers, hipStream_t s);  // total[i] = sum over k of layers[k * n + i]
+void LaunchMCSumLayers(const float *layers, float *total, size_t n, int nLayers, hipStream_t s);          // ... float adds in increasing k
 long long MCThreads(const lmcd::DScene &S, long long streamBegin, long long streamEnd);
 void LaunchMCFixedToFloat(const long long *fx, float *rgb, size_t n, int spp, hipStream_t s);  // rgb[i] = float(double(fx[i]) * 2^-32 / double(spp))
 void LaunchSetupChains(const lmcd::ChainArrays &A, int chainBegin, long long perChain, long long chainsNeedExtra, hipStream_t s);

@@ -380,6 +380,10 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
     else if (n == "mc_film_exact") {  // the mc film's accumulator (device/mc.hip): takes effect at the next lmc_mc_render
         c->mcExactOpt = v != 0;
         return 0;
+    } else if (n == "mc_layers") {  // the mc film split by path length (1) or technique (2), host/mcrender.cpp: takes effect at the next lmc_mc_render
+        if (v != 0 && v != 1 && v != 2) throw std::runtime_error("mc_layers: 0 (off), 1 (by path length) or 2 (by technique) expected");
+        c->mcLayersOpt = (int)v;
+        return 0;
     } else if (n == "mc_launch_streams") {  // stream ids per launch of lmc_mc_render / lmc_mc_accumulate
         if (!(v >= 1 && v <= 1e12)) throw std::runtime_error("mc_launch_streams: at least 1 stream id per launch expected");
         c->mcLaunchStreams = (long long)v;
@@ -427,6 +431,7 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "bvh_thick_flat_share") *v = c->thickFlatShare;       // ... and the figure it was chosen by (UploadScene)
     else if (n == "film_exact") *v = c->filmExact ? 1 : 0;
     else if (n == "mc_film_exact") *v = c->mcExactOpt ? 1 : 0;
+    else if (n == "mc_layers") *v = c->mcLayersOpt;
     else if (n == "mc_launch_streams") *v = (double)c->mcLaunchStreams;
     else if (n == "mc_launches") *v = c->mcLaunches;  // launches of the last lmc_mc_render / lmc_mc_accumulate
     else if (n == "resident_steps") *v = c->residentSteps;

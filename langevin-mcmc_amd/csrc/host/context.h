@@ -111,6 +111,14 @@ struct lmc_ctx {
     lmc::McCoverage mcCoverage;  // the stream ids mcFilmFx holds
     long long mcLaunchStreams = 262144;  // "mc_launch_streams": stream ids per launch of a render / accumulate call, either mode
     int mcLaunches = 0;                  // "mc_launches": launches of the last such call
+    // the layered mc film ("mc_layers", INTEGRATION.md "Layered mc film"): mcNLayers films of W*H*3 words one after the other (exact: one overflow word behind
+    // them), split by path length (mode 1) or technique (mode 2).  mcFilm / mcFilmFx then hold their sum, made after every render / accumulate call, so
+    // every call that reads the film sees the total.
+    DevBuf<float> mcLayersF;
+    DevBuf<long long> mcLayersFx;
+    int mcLayersOpt = 0;   // the option: read by the next lmc_mc_render
+    int mcLayerMode = 0;   // the mode of the film the context holds (0: unlayered)
+    int mcNLayers = 0;
     int world = 1, rank = 0;          // position in the job (lmc_comm_init: RCCL ranks; lmc_group_chains_init: in-process group)
     std::vector<lmc_ctx *> group;    // in-process group this context is a member of (empty / 1: none)
     bool filmReduced = false;  // the device film + weightSum already hold the all-reduced sums (lmc_film_allreduce is in place)

@@ -77,6 +77,8 @@ static int PathTracePass(lmc_ctx *c, int directSpp, int minDepth, int maxDepth) 
 // the integer sum of the unweighted contributions, knows which stream ids it holds (host/mcfilm.h McCoverage) and is divided by spp when it is read, so
 // calls can add to it (lmc_mc_accumulate), members' films can be summed in any order (lmc_group_mc_render) and a file can carry it (lmc_mc_save / _load).
 // Either mode runs a call as launches of at most "mc_launch_streams" stream ids on the context's stream.
+// Layered ("mc_layers", INTEGRATION.md "Layered mc film"): the launches add to mcLayersF / mcLayersFx, one film per path length or technique, and every call ends
+// with the sum of the layers in mcFilm / mcFilmFx (overflow word included), so whatever reads the film below reads the total and needs no second form.
 namespace {
 long long McTiles(const lmc_ctx *c) { return (long long)((c->S.cam.width + 15) / 16) * ((c->S.cam.height + 15) / 16); }
 size_t McWords(const lmc_ctx *c) { return (size_t)c->S.cam.width * c->S.cam.height * 3; }
@@ -89,22 +91,62 @@ void McCheckRange(const char *what, lmc_ctx *c, int spp, long long &begin, long 
         throw std::runtime_error(std::string(what) + ": stream range [" + std::to_string(begin) + ", " + std::to_string(end) + ") outside [0, " + std::to_string(total) + ")");
 }
 
-// the launches of one call: [begin, end) in chunks (mcfilm.h McChunks), one table scratch sized for the largest of them, one wait at the end
-void McRunLaunches(lmc_ctx *c, const Film &film, int spp, long long begin, long long end) {
+// the film of a context set to layer mode `mode` (the option's value): the layer count, the buffer allocated if its size changed, and cleared
+void McStartLayers(const char *what, lmc_ctx *c, int mode, bool exact) {
+    c->mcLayerMode = 0, c->mcNLayers = 0;  // (a refusal below leaves an unlayered context)
+    if (mode == 0) {
+        c->mcLayersF.Free(), c->mcLayersFx.Free();
+        return;
+    }
+    const int D = c->S.opt.maxDepth;
+    if (D < 1 || D > 12) throw std::runtime_error(std::string(what) + ": mc_layers = " + std::to_string(mode) + " needs a maxdepth of 1 .. 12, the scene's is " + std::to_string(D));
+    const int n = McLayerCount(mode, D);
+    if ((unsigned long long)n * c->S.cam.width * c->S.cam.height * 3 > 0x7fffffffull)
+        throw std::runtime_error(std::string(what) + ": mc_layers = " + std::to_string(mode) + ": " + std::to_string(n) + " layers of this film size exceed 2^31 words");
+    const size_t words = (size_t)n * McWords(c) + (exact ? 1 : 0), bytes = words * (exact ? sizeof(long long) : sizeof(float));
+    try {
+        if (exact) {
+            c->mcLayersF.Free();
+            if (c->mcLayersFx.n != words) c->mcLayersFx.Alloc(words, false);
+        } else {
+            c->mcLayersFx.Free();
+            if (c->mcLayersF.n != words) c->mcLayersF.Alloc(words, false);
+        }
+    } catch (const std::exception &e) {
+        throw std::runtime_error(std::string(what) + ": cannot allocate the " + std::to_string(bytes) + " bytes of the layered mc film (mc_layers = " + std::to_string(mode) + ", " +
+                                 std::to_string(n) + " layers): " + e.what());
+    }
+    HIP_CHECK(hipMemsetAsync(exact ? (void *)c->mcLayersFx.p : (void *)c->mcLayersF.p, 0, bytes, c->stream));
+    c->mcLayerMode = mode, c->mcNLayers = n;
+}
+
+// the launches of one call: [begin, end) in chunks (mcfilm.h McChunks), one table scratch sized for the largest of them, one wait at the end; a layered
+// film's launches go to the layers, and their sum is made before the wait
+void McRunLaunches(lmc_ctx *c, Film film, int spp, long long begin, long long end) {
     const std::vector<lmc::McRange> chunks = lmc::McChunks(begin, end, McTiles(c), c->mcLaunchStreams);
     long long maxThreads = 0;
     for (const lmc::McRange &r : chunks) maxThreads = std::max(maxThreads, MCThreads(c->S, r.first, r.second));
     DevBuf<uint32_t> tab;  // written only by a stream that ticks (once per 2^32 draws)
     tab.Alloc((size_t)((maxThreads + 63) / 64 * 64) * 64, false);
+    const bool exact = (film.H & FILM_EXACT) != 0;
+    if (c->mcLayerMode) film.rgb = exact ? reinterpret_cast<float *>(c->mcLayersFx.p) : c->mcLayersF.p;
     for (const lmc::McRange &r : chunks)
-        LaunchMC(c->S, film, c->scene->options.bidirectional, spp, c->S.opt.minDepth, c->S.opt.maxDepth, r.first, r.second, tab.p, c->mcCounters.p, c->stream);
+        LaunchMC(c->S, film, c->mcLayerMode, c->mcNLayers, c->scene->options.bidirectional, spp, c->S.opt.minDepth, c->S.opt.maxDepth, r.first, r.second, tab.p, c->mcCounters.p,
+                 c->stream);
+    if (c->mcLayerMode && exact) {
+        LaunchMCSumLayers(c->mcLayersFx.p, c->mcFilmFx.p, McWords(c), c->mcNLayers, c->stream);
+        HIP_CHECK(hipMemcpyAsync(c->mcFilmFx.p + McWords(c), c->mcLayersFx.p + (size_t)c->mcNLayers * McWords(c), sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+    } else if (c->mcLayerMode) {
+        LaunchMCSumLayers(c->mcLayersF.p, c->mcFilm.p, McWords(c), c->mcNLayers, c->stream);
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
     c->mcLaunches = (int)chunks.size();
 }
 
-// an empty exact film: words, overflow word, counters and coverage cleared
-void McStartExact(lmc_ctx *c) {
+// an empty exact film: words, overflow word, counters and coverage cleared; layered as the option says
+void McStartExact(const char *what, lmc_ctx *c) {
+    McStartLayers(what, c, c->mcLayersOpt, true);
     if (c->mcFilmFx.n != McWords(c) + 1) c->mcFilmFx.Alloc(McWords(c) + 1, false);
     if (c->mcCounters.n != 2) c->mcCounters.Alloc(2, false);
     HIP_CHECK(hipMemsetAsync(c->mcFilmFx.p, 0, c->mcFilmFx.n * sizeof(long long), c->stream));
@@ -123,7 +165,7 @@ void McAccumulate(const char *what, lmc_ctx *c, int spp, long long begin, long l
     if (c->mcCoverage.Overlaps(begin, end))
         throw std::runtime_error(std::string(what) + ": stream range [" + std::to_string(begin) + ", " + std::to_string(end) +
                                  ") overlaps what the film already holds (its samples would be counted twice); the film is unchanged");
-    McRunLaunches(c, FilmFx(c->mcFilmFx.p, c->S.cam.width, c->S.cam.height), spp, begin, end);
+    McRunLaunches(c, FilmFx(c->mcFilmFx.p, c->S.cam.width, c->S.cam.height), spp, begin, end);  // (a layered film: into its layers, mcFilmFx their sum)
     c->mcCoverage.Add(begin, end);
     c->mcDivisor = spp;
 }
@@ -148,11 +190,12 @@ int lmc_mc_render(lmc_ctx *c, int spp, long long streamBegin, long long streamEn
     McCheckRange("lmc_mc_render", c, spp, streamBegin, streamEnd);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     if (c->mcExactOpt) {
-        McStartExact(c);
+        McStartExact("lmc_mc_render", c);
         McAccumulate("lmc_mc_render", c, spp, streamBegin, streamEnd);
         return 0;
     }
     const int W = c->S.cam.width, H = c->S.cam.height;
+    McStartLayers("lmc_mc_render", c, c->mcLayersOpt, false);
     c->mcFilmIsExact = false;
     c->mcCoverage.Clear();
     if (c->mcFilm.n != (size_t)W * H * 3) c->mcFilm.Alloc((size_t)W * H * 3, false);
@@ -169,7 +212,10 @@ int lmc_mc_accumulate(lmc_ctx *c, int spp, long long streamBegin, long long stre
     HIP_CHECK(hipSetDevice(c->device));
     McCheckRange("lmc_mc_accumulate", c, spp, streamBegin, streamEnd);
     HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (!c->mcFilmIsExact) McStartExact(c);  // no exact film yet: an empty one
+    if (c->mcFilmIsExact && c->mcLayerMode != c->mcLayersOpt)
+        throw std::runtime_error("lmc_mc_accumulate: the film the context holds was rendered with mc_layers = " + std::to_string(c->mcLayerMode) + ", the option is now mc_layers = " +
+                                 std::to_string(c->mcLayersOpt) + "; a film takes more samples in its own layer mode only, and is unchanged");
+    if (!c->mcFilmIsExact) McStartExact("lmc_mc_accumulate", c);  // no exact film yet: an empty one
     McAccumulate("lmc_mc_accumulate", c, spp, streamBegin, streamEnd);
     return 0;
     LMC_CATCH(-1)
@@ -228,6 +274,56 @@ int lmc_mc_stats(lmc_ctx *c, long long *out2) {
     LMC_CATCH(-1)
 }
 
+// The layers of the film the context holds (include/lmc_abi.h "Layered mc film")
+int lmc_mc_layer_info(lmc_ctx *c, int *mode, int *nLayers, int *cl, int cap) {
+    LMC_TRY
+    const bool have = c->mcLayerMode != 0 && (c->mcFilmIsExact ? c->mcLayersFx.n != 0 : c->mcLayersF.n != 0);
+    if (mode) *mode = have ? c->mcLayerMode : 0;
+    if (nLayers) *nLayers = have ? c->mcNLayers : 0;
+    if (!have || !cl) return 0;
+    int k = 0;
+    for (int L = 1; k < c->mcNLayers; L++)
+        for (int l = 0; l <= (c->mcLayerMode == 2 ? L : 0) && k < c->mcNLayers; l++, k++)
+            if (k < cap) cl[2 * k] = c->mcLayerMode == 2 ? L + 1 - l : L, cl[2 * k + 1] = c->mcLayerMode == 2 ? l : -1;
+    return 0;
+    LMC_CATCH(-1)
+}
+static void McCheckLayer(const char *what, lmc_ctx *c, int layer) {
+    if (c->mcLayerMode == 0 || c->mcNLayers == 0) throw std::runtime_error(std::string(what) + ": the context holds no layered mc film (lmc_set_option \"mc_layers\" = 1 or 2 before lmc_mc_render)");
+    if (layer < 0 || layer >= c->mcNLayers)
+        throw std::runtime_error(std::string(what) + ": layer " + std::to_string(layer) + " outside [0, " + std::to_string(c->mcNLayers) + ") of the film (mc_layers = " + std::to_string(c->mcLayerMode) + ")");
+}
+int lmc_mc_read_layer(lmc_ctx *c, int layer, float *rgb) {
+    LMC_TRY
+    McCheckLayer("lmc_mc_read_layer", c, layer);
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    const size_t words = McWords(c);
+    if (!c->mcFilmIsExact) {
+        HIP_CHECK(hipMemcpy(rgb, c->mcLayersF.p + (size_t)layer * words, words * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (c->mcDivisor < 1) throw std::runtime_error("lmc_mc_read_layer before lmc_mc_render");
+    DevBuf<float> conv;  // converted on the device like lmc_mc_read, float(double(q) * 2^-32 / double(spp))
+    conv.Alloc(words, false);
+    LaunchMCFixedToFloat(c->mcLayersFx.p + (size_t)layer * words, conv.p, words, c->mcDivisor, c->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(hipMemcpy(rgb, conv.p, words * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+    LMC_CATCH(-1)
+}
+int lmc_mc_read_layer_fixed(lmc_ctx *c, int layer, long long *out) {
+    LMC_TRY
+    if (!c->mcFilmIsExact) throw std::runtime_error("lmc_mc_read_layer_fixed: the mc film is in float mode (lmc_set_option \"mc_film_exact\" = 1 before lmc_mc_render)");
+    McCheckLayer("lmc_mc_read_layer_fixed", c, layer);
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(hipMemcpy(out, c->mcLayersFx.p + (size_t)layer * McWords(c), McWords(c) * sizeof(long long), hipMemcpyDeviceToHost));
+    return 0;
+    LMC_CATCH(-1)
+}
+
 }  // extern "C"
 
 // [begin, end) split at begin + (end - begin) * k / n, the shards rendered concurrently (one host thread per member), then member 0's film += member k's for
@@ -243,6 +339,9 @@ static int GroupMcRender(const char *what_, bool accumulate, lmc_ctx **ctxs, int
         if (!g[r]) throw std::runtime_error(what + ": null member");
         for (int q = 0; q < r; q++)
             if (g[q] == g[r]) throw std::runtime_error(what + ": a context is listed twice (a device may be, through a context of its own)");
+        if (g[r]->mcLayersOpt != 0 || (accumulate && r == 0 && g[0]->mcFilmIsExact && g[0]->mcLayerMode != 0))
+            throw std::runtime_error(what + ": member " + std::to_string(r) + " is set to mc_layers = " + std::to_string(g[r]->mcLayersOpt ? g[r]->mcLayersOpt : g[r]->mcLayerMode) +
+                                     "; in this version a layered mc film is rendered by one context, not by a group (nothing was rendered)");
         if (g[r]->mcExactOpt != g[0]->mcExactOpt)
             throw std::runtime_error(what + ": the members differ in mc_film_exact (member 0: " + std::to_string((int)g[0]->mcExactOpt) + ", member " + std::to_string(r) + ": " +
                                      std::to_string((int)g[r]->mcExactOpt) + "); a group's films are summed in one format");
@@ -315,6 +414,8 @@ int lmc_group_mc_accumulate(lmc_ctx **ctxs, int n, int spp, long long streamBegi
 int lmc_mc_save(lmc_ctx *c, const char *path) {
     LMC_TRY
     if (!path) throw std::runtime_error("lmc_mc_save: no path");
+    if (c->mcLayerMode != 0)
+        throw std::runtime_error("lmc_mc_save: the mc film is layered (mc_layers = " + std::to_string(c->mcLayerMode) + "); in this version a state file holds an unlayered film only (nothing was written)");
     if (!c->mcFilmIsExact || c->mcFilmFx.n == 0) throw std::runtime_error("lmc_mc_save: the context holds no exact mc film (lmc_set_option \"mc_film_exact\" = 1 before lmc_mc_render)");
     HIP_CHECK(hipSetDevice(c->device));
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -330,6 +431,8 @@ int lmc_mc_save(lmc_ctx *c, const char *path) {
 int lmc_mc_load(lmc_ctx *c, const char *path) {
     LMC_TRY
     if (!path) throw std::runtime_error("lmc_mc_load: no path");
+    if (c->mcLayersOpt != 0)
+        throw std::runtime_error("lmc_mc_load: the context is set to mc_layers = " + std::to_string(c->mcLayersOpt) + "; in this version a state file holds an unlayered film only (the context is unchanged)");
     if (!c->mcExactOpt) throw std::runtime_error("lmc_mc_load: the mc film is in float mode; a state file holds an exact film (lmc_set_option \"mc_film_exact\" = 1)");
     std::vector<long long> words;
     const lmc::McFileHeader F = lmc::McFileRead(path, &words);
@@ -340,7 +443,7 @@ int lmc_mc_load(lmc_ctx *c, const char *path) {
     HIP_CHECK(hipStreamSynchronize(c->stream));
     words.push_back(F.overflow);
     const unsigned long long counters[2] = {(unsigned long long)F.paths, (unsigned long long)F.contributions};
-    McStartExact(c);
+    McStartExact("lmc_mc_load", c);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(c->mcFilmFx.p, words.data(), words.size() * sizeof(long long), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(c->mcCounters.p, counters, sizeof(counters), hipMemcpyHostToDevice));

@@ -27,6 +27,9 @@
 // --devices list, for any cut into legs, and from run to run.  There --spp N overrides <dpt spp>, --max-spp K renders the sample indices below K only
 // and writes the image with divisor K, --checkpoint F writes the film's state file (lmc_mc_save) at the end and --resume F loads one and renders what
 // its coverage lacks of [0, nTiles * spp); both need the exact film (a resume takes the mode from the file).
+// --mc-layers length|technique (mc scenes only; lmc_set_option "mc_layers", INTEGRATION.md "Layered mc film"): the render split by path length or by technique.
+// The usual EXR holds the sum of the layers; beside it every non-empty layer is written under the same name with _L<length> (two digits) or
+// _c<camDepth>_l<lightDepth> before .exr.  One device, no --checkpoint / --resume in this version.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -59,6 +62,7 @@ struct McFlags {
     bool exactFilm = false;
     int spp = 0, maxSpp = 0;  // --spp / --max-spp (0: not given)
     std::string checkpointPath, resumePath;
+    int layers = 0;  // --mc-layers: 1 length, 2 technique
 };
 
 // integrator = mc: the stream range [0, nTiles * spp) split into contiguous shards, one per context, rendered concurrently and summed on member 0's
@@ -89,10 +93,25 @@ static int RenderMC(const std::string &filename, std::vector<lmc_ctx *> &ctxs, c
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
         }
+    if (F.layers != 0) {
+        if (nDev > 1 || !F.checkpointPath.empty() || !F.resumePath.empty()) {
+            fprintf(stderr, "--mc-layers: a layered mc film is rendered on one device and has no state file in this version (no --gpus / --devices list, --checkpoint or --resume)\n");
+            return 2;
+        }
+        if (lmc_set_option(ctx, "mc_layers", F.layers) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+    }
     if (exact) printf("Exact film: 64-bit fixed-point accumulation\n");
     if (nDev > 1) printf("%lld sample streams sharded over %d devices\n", total, nDev);
     auto t0 = std::chrono::steady_clock::now();
-    if (F.resumePath.empty()) {
+    if (F.layers != 0) {
+        if (lmc_mc_render(ctx, spp, 0, total) != 0) {
+            fprintf(stderr, "%s\n", lmc_last_error());
+            return 1;
+        }
+    } else if (F.resumePath.empty()) {
         if (lmc_group_mc_render(ctxs.data(), nDev, spp, 0, total) != 0) {
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
@@ -151,6 +170,33 @@ static int RenderMC(const std::string &filename, std::vector<lmc_ctx *> &ctxs, c
         fprintf(stderr, "%s\n", lmc_last_error());
         return 1;
     }
+    if (F.layers != 0) {  // every non-empty layer beside the image
+        int mode = 0, nLayers = 0, written = 0;
+        std::vector<int> cl(2 * 128);
+        if (lmc_mc_layer_info(ctx, &mode, &nLayers, cl.data(), 128) != 0 || nLayers > 128) {
+            fprintf(stderr, "%s\n", nLayers > 128 ? "--mc-layers: more than 128 layers" : lmc_last_error());
+            return 1;
+        }
+        std::vector<float> layer((size_t)W * H * 3);
+        for (int k = 0; k < nLayers; k++) {
+            if (lmc_mc_read_layer(ctx, k, layer.data()) != 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+            if (std::all_of(layer.begin(), layer.end(), [](float v) { return v == 0.0f; })) continue;
+            char tag[64];
+            if (mode == 1) snprintf(tag, sizeof(tag), "_L%02d", cl[2 * k]);
+            else
+                snprintf(tag, sizeof(tag), "_c%d_l%d", cl[2 * k], cl[2 * k + 1]);
+            const std::string name = out.substr(0, out.size() - 4) + tag + ".exr";
+            if (lmc_image_write_exr(name.c_str(), layer.data(), W, H) != 0) {
+                fprintf(stderr, "%s\n", lmc_last_error());
+                return 1;
+            }
+            written++;
+        }
+        printf("Layered film (%s): %d of %d layers are non-empty and written beside the image\n", mode == 1 ? "by path length" : "by technique", written, nLayers);
+    }
     if (dropped > 0) printf("Exact film: %lld contributions with a component of 2^30 or more were dropped\n", dropped);
     printf("%lld paths, %lld contributions, %.1f M paths/s, wrote %s\n", st[0], st[1], st[0] / elapsed * 1e-6, out.c_str());
     return 0;
@@ -164,6 +210,7 @@ int main(int argc, char *argv[]) {
     std::string checkpointPath, resumePath;
     bool exactFilm = false;
     int mcSpp = 0, mcMaxSpp = 0;  // --spp / --max-spp (integrator = mc)
+    int mcLayers = 0;              // --mc-layers length|technique (integrator = mc)
     bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -198,6 +245,14 @@ int main(int argc, char *argv[]) {
         else if (a == "--exact-film") exactFilm = true;
         else if (a == "--spp") mcSpp = std::stoi(argv[++i]);
         else if (a == "--max-spp") mcMaxSpp = std::stoi(argv[++i]);
+        else if (a == "--mc-layers") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            mcLayers = m == "length" ? 1 : m == "technique" ? 2 : 0;
+            if (mcLayers == 0) {
+                fprintf(stderr, "--mc-layers: length or technique expected\n");
+                return 2;
+            }
+        }
         else filenames.push_back(a);
     }
     if (devices.empty()) devices.push_back(device);
@@ -227,12 +282,17 @@ int main(int argc, char *argv[]) {
         if (Opt(ctx, "integrator_mc") != 0) {  // main.cpp:92-96
             if (mltFlags) printf("--chains / --resident / --init-threads: ignored by integrator=mc\n");
             McFlags mf;
+            mf.layers = mcLayers;
             mf.exactFilm = exactFilm, mf.spp = mcSpp, mf.maxSpp = mcMaxSpp, mf.checkpointPath = checkpointPath, mf.resumePath = resumePath;
             const int rc = RenderMC(filename, ctxs, mf);
             for (lmc_ctx *c : ctxs) lmc_destroy(c);
             if (rc != 0) return rc;
             printf("Done!\n");
             continue;
+        }
+        if (mcLayers != 0) {
+            fprintf(stderr, "--mc-layers: %s has integrator=mcmc; only the film of an integrator=mc scene can be layered\n", filename.c_str());
+            return 2;
         }
         if (Opt(ctx, "mala") == 0 && Opt(ctx, "h2mc") == 0) {
             fprintf(stderr, "dpt_amd serves the LMC path only (<dpt> integrator=mcmc with mala=true or h2mc=true)\n");
