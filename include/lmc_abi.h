@@ -298,7 +298,8 @@ int lmc_cache_rows(lmc_ctx *ctx, int dim, float *pss, float *weight, float *extr
 int lmc_cache_probe(lmc_ctx *ctx, int dim, int n, const float *u, int *row, const float *query, const int *cl, float *pdf);
 
 /* ---- probes used by the parity tests (tests/) ---- */
-/* rays: n x [ox,oy,oz,dx,dy,dz,tnear,tfar]; closest hit -> global triangle id (or -1) and t */
+/* rays: n x [ox,oy,oz,dx,dy,dz,tnear,tfar]; closest hit -> global triangle id (or -1) and t
+ * (environment LMC_TRACE_TIGHT=1, read at every call: both walks fetch a leaf's triangles two per round, as the three-wave lean launches do) */
 int lmc_trace(lmc_ctx *ctx, int n, const float *rays, int *prim, float *t);
 int lmc_occluded(lmc_ctx *ctx, int n, const float *rays, int *occluded);
 /* mode 0 raw u32, 1 uniform01 bits, 2 one normal_distribution object, 3 mixed (u,u,7 normals per round); + 8: the extension table synthesised from
@@ -310,6 +311,13 @@ int lmc_kd_probe(int dim, int npts, const float *pts, int nq, const float *q, fl
 int lmc_lower_bound_probe(int n, const float *cdf, int nq, const float *u, int *out);
 /* measurement aid: ms per launch of a kernel that streams `words` state words per chain in batches of `batch` loads; mode 0 = [word][chain], 1 = [tile of 64][word][lane] */
 int lmc_layout_probe(int nChains, int words, int mode, int batch, int reps, double *msPerLaunch);
+/* test hook (no device): the LDS plan of the lean small-step launch for a tree whose traversal stack needs bvh_stack_need entries: the stack words of a
+ * thread (the need rounded up to 4, at least 24), its LDS words in all (+ 24), and the dynamic bytes of a block of block_threads */
+int lmc_lean_plan_probe(int bvh_stack_need, int block_threads, int *stack_words, int *lds_words_per_thread, long long *lds_bytes_per_block);
+/* what the context's lean small-step launch is (no launch): out16[0 .. 7] = leaves of the uploaded tree that hold 1 .. 8 triangles, [8] = the tree's stack
+ * need, [9] = LDS stack words of a thread, [10 .. 14] = the instantiation of k_step_small it takes: LDS stack, glossy, without light sub-paths, quantised
+ * nodes, the register-saving forms of the three-wave launches (two leaf triangles per round), [15] = threads per block */
+int lmc_lean_info(lmc_ctx *ctx, int *out16);
 /* parity probe, evaluated on the device: the deterministic float exp (mode 0) / log (1) / pow (2) of the glossy BSDFs (device/dtrans.h), sin (3) / cos (4) /
  * acos (5) / atan2(x, y) (6) of the sampling code (device/dtrig.h), and glibc's logf as restated for the normal distribution (7, device/drng.h) */
 int lmc_trans_probe(int n, int mode, const float *x, const float *y, float *out);

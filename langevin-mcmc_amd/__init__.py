@@ -478,6 +478,17 @@ class Renderer:
             raise RuntimeError(_err())
         return {"lean_ms": out[0], "large_ms": out[1], "generic_ms": out[2], "lean_steps": int(out[3])}
 
+    def lean_info(self):
+        """The lean small-step launch of this context (lmc_lean_info): leaves of the tree by triangle count, stack need, LDS stack words and
+        which instantiation of the kernel it takes"""
+        out = (ctypes.c_int * 16)()
+        L = lib()
+        L.lmc_lean_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        if L.lmc_lean_info(self.h, out) != 0:
+            raise RuntimeError(_err())
+        v = list(out)
+        return dict(leaf_hist=v[:8], stack_need=v[8], stack_words=v[9], lds=v[10], glossy=v[11], lightless=v[12], quant=v[13], tight=v[14], block=v[15])
+
     def trace(self, rays):
         rays = np.ascontiguousarray(rays, np.float32)
         n = len(rays)

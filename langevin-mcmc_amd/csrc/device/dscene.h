@@ -204,10 +204,16 @@ constexpr int BVH_LDS_STACK = 40;
 // when the scene is loaded (host/context.cpp UploadScene: the quantised nodes suit a tree unless it is full of flat leaves away from their node's
 // faces -- accel.h ThickenedFlatLeafShare) and compiled in as a template parameter of the two hot launches (the lean small steps, the large
 // steps): a run-time branch inside the kernels cost more than the smaller nodes save (profiles/r04_nodes_a_*).
-template <bool GLOSSY, bool QUANT = false>
+// ... and kTight (the Lambertian lightless lean launches, which run three waves per SIMD on 168 registers; step_small_plain.hip): the forms that
+// trade a few instructions for registers.  kLeafRound: a leaf's triangles are fetched two per round instead of four (2 x 12 words in flight; tests in
+// leaf order, tie rule untouched); dsmall.h reads kTight where it forms the chain's addresses and clears the contribution record.  Every other
+// launch compiles to what it was (profiles/r14_lean_tight_resources.txt).
+template <bool GLOSSY, bool QUANT = false, bool TIGHT = false>
 struct LocalStackT {
     static constexpr bool kGlossy = GLOSSY;
     static constexpr bool kQuant = QUANT;
+    static constexpr bool kTight = TIGHT;
+    static constexpr int kLeafRound = TIGHT ? 2 : 4;
     int s[BVH_STACK];
     int sp = 0;
     LMC_D void Reset() { sp = 0; }
@@ -217,10 +223,12 @@ struct LocalStackT {
     }
     LMC_D int Pop() { return s[--sp]; }
 };
-template <bool GLOSSY, bool QUANT = false>
+template <bool GLOSSY, bool QUANT = false, bool TIGHT = false>
 struct LdsStackT {
     static constexpr bool kGlossy = GLOSSY;
     static constexpr bool kQuant = QUANT;
+    static constexpr bool kTight = TIGHT;
+    static constexpr int kLeafRound = TIGHT ? 2 : 4;
     int *base;   // &lds[threadIdx.x]
     int stride;  // blockDim.x
     int sp;      // the top's word offset from base = entries x stride, advanced by additions: with an entry COUNT every push and pop paid a 32-bit
@@ -236,6 +244,10 @@ struct LdsStackT {
         return base[sp * stride];
     }
 #else
+    // The guard is the 40 entries of BVH_LDS_STACK, NOT the words the launch reserved: the lean launches reserve the tree's own stack need rounded up to 4
+    // (dsmall.h LeanStackWords) and keep the proposal offsets right behind it.  What keeps a push inside that region is the host's bound (accel.cpp
+    // Collapse: `pending + n - 1`) together with the discipline of VisitNode4 / VisitNode4Q: a visit keeps its nearest hit child in a register and pushes
+    // at most the n - 1 others.  A walk that pushed every hit child before popping one would need one entry more than the bound.
     LMC_D void Push(int v) {
         if (sp < BVH_LDS_STACK * stride) base[sp] = v, sp += stride;
     }
@@ -346,11 +358,13 @@ LMC_D int VisitNode4Q(const BvhNode4Q &nd, V3 org, V3 invd, float tnear, float t
 // `global_load_dwordx3` per triangle behind `v_cmp_neq_f32 divisor`).  An empty asm that names the registers as in / out pins the loads where
 // the source has them: all of a visit's loads are in flight together.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(LMC_NO_LOAD_PIN)
+#define LMC_PIN1(a) asm volatile("" : "+v"(a))
 #define LMC_PIN2(a, b) asm volatile("" : "+v"(a), "+v"(b))
 #define LMC_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
 #define LMC_PIN5(a, b, c, d, e) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e))
 #define LMC_PIN4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 #else
+#define LMC_PIN1(a) ((void)0)
 #define LMC_PIN2(a, b) ((void)0)
 #define LMC_PIN3(a, b, c) ((void)0)
 #define LMC_PIN5(a, b, c, d, e) ((void)0)
@@ -414,14 +428,15 @@ LMC_D int BvhIntersect(const DScene &S, V3 org, V3 dir, float tnear, float tfar,
         if (cur < 0) {
             const unsigned code = (unsigned)~cur;
             const int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
-            for (int base = 0; base < cnt; base += 4) {
-                LeafTri tr[4];
+            constexpr int R = Stk::kLeafRound;  // as in the loop of the default build below
+            for (int base = 0; base < cnt; base += R) {
+                LeafTri tr[R];
 #pragma unroll
-                for (int i = 0; i < 4; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
+                for (int i = 0; i < R; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
 #pragma unroll
-                for (int i = 0; i < 4; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
+                for (int i = 0; i < R; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
+                for (int i = 0; i < R; i++) {
                     float t;
                     if (base + i < cnt && TriTest(tr[i].p0, tr[i].e1, tr[i].e2, org, dir, tnear, bestT, t)) {
                         if (best < 0 || t < bestT || (t == bestT && tr[i].id < best)) {
@@ -451,14 +466,15 @@ LMC_D int BvhIntersect(const DScene &S, V3 org, V3 dir, float tnear, float tfar,
         }
         const unsigned code = (unsigned)~cur;
         const int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
-        for (int base = 0; base < cnt; base += 4) {
-            LeafTri tr[4];
+        constexpr int R = Stk::kLeafRound;  // triangles in flight per round
+        for (int base = 0; base < cnt; base += R) {
+            LeafTri tr[R];
 #pragma unroll
-            for (int i = 0; i < 4; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
+            for (int i = 0; i < R; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
 #pragma unroll
-            for (int i = 0; i < 4; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
+            for (int i = 0; i < R; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
+            for (int i = 0; i < R; i++) {
                 float t;
                 if (base + i < cnt && TriTest(tr[i].p0, tr[i].e1, tr[i].e2, org, dir, tnear, bestT, t)) {
                     if (best < 0 || t < bestT || (t == bestT && tr[i].id < best)) {
@@ -492,14 +508,15 @@ LMC_D bool BvhOccluded(const DScene &S, V3 org, V3 dir, float tnear, float tfar,
         const unsigned code = (unsigned)~cur;
         const int first = (int)(code >> 3), cnt = (int)(code & 7u) + 1;
         bool hit = false;
-        for (int base = 0; base < cnt; base += 4) {
-            LeafTri tr[4];
+        constexpr int R = Stk::kLeafRound;
+        for (int base = 0; base < cnt; base += R) {
+            LeafTri tr[R];
 #pragma unroll
-            for (int i = 0; i < 4; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
+            for (int i = 0; i < R; i++) tr[i] = S.leafTris[first + min(base + i, cnt - 1)];
 #pragma unroll
-            for (int i = 0; i < 4; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
+            for (int i = 0; i < R; i++) LMC_PIN3(tr[i].p0[0], tr[i].p0[1], tr[i].p0[2]);
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
+            for (int i = 0; i < R; i++) {
                 float t;
                 if (base + i < cnt && TriTest(tr[i].p0, tr[i].e1, tr[i].e2, org, dir, tnear, tfar, t)) hit = true;
             }

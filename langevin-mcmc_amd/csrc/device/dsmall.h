@@ -29,18 +29,24 @@ namespace lmcd {
 // PSS_MAX_LENGTH always get IsotropicGaussian(malaStdDev), which needs no per-dimension storage at all.
 constexpr int MD = PSS_MAX_LENGTH;
 
-// LDS words per thread, S = the launch's BVH stack entries (the scene's stack need rounded up to 8, at least 32, at most
-// BVH_LDS_STACK: 32 for the torus = 56 words = 14 KB per wave, 11 waves per CU; 40 for the veach-door scene):
-//   [0, S)          the BVH stack; between traversals the staged Gaussian / moment vectors / clipped gradient (2 MD <= 32 words)
+// LDS words per thread, S = the launch's BVH stack entries (the scene's stack need rounded up to 4, at least 2 MD = 24, at most
+// BVH_LDS_STACK: 28 for the torus, whose tree needs 27, = 52 words = 13 312 B per wave; with the 1 280 static bytes of the jump and logf tables, which every
+// block holds, eleven one-wave blocks per CU (the default block, host/context.h leanBlock) or three blocks of 256 = twelve waves: the one-wave blocks
+// are faster, profiles/r14_lean_tight_ab.md; 40 for the veach-door scene, which needs 37):
+//   [0, S)          the BVH stack; between traversals the staged Gaussian / moment vectors / clipped gradient (2 MD = 24 words)
 //   [S, S + 12)     the proposal offsets of a state with dim <= MD
 //   [S + 12, S + 24) its new primary-sample vector
 //   [S, S + 24)     the offsets of a state with dim > MD (up to 2 * MAXD): such a state is never looked up, it has no Q
+// The host's stack need is an upper bound (accel.cpp Collapse: while a child is walked at most its n - 1 siblings are pending) that holds for walks which
+// keep the nearest hit child in a register and push only the others (dscene.h VisitNode4 / VisitNode4Q, LdsStackT::Push), so S carries no slack above it.
+// The launches that size their LDS with this function -- k_step_small, k_step_small_grad, k_h2_perturb_streamed, k_lean_query_probe (need 0: 24 words) --
+// all shrink with it; their staging stays inside 2 MD words.
 // The kd-tree search frames used to live here too (80 words, 8 waves per CU).  Since the existence test (dchain.h) the search
 // runs for 0.015 % of the queries: it now keeps its frames in private memory, out of line (KdRadiusSearchRare).
-constexpr int LDS_MIN_STACK_WORDS = 32;
-static_assert(2 * MD <= LDS_MIN_STACK_WORDS, "the staging words live in the (idle) stack region");
+constexpr int LDS_MIN_STACK_WORDS = 2 * MD;
+static_assert(2 * MD <= LDS_MIN_STACK_WORDS && LDS_MIN_STACK_WORDS % 4 == 0, "the staging words (filled in groups of four) live in the (idle) stack region");
 LMC_HD int LeanStackWords(int bvhStackNeed) {
-    const int w = (bvhStackNeed + 7) / 8 * 8;
+    const int w = (bvhStackNeed + 3) / 4 * 4;
     return w < LDS_MIN_STACK_WORDS ? LDS_MIN_STACK_WORDS : w;
 }
 LMC_HD int LeanLdsWordsPerThread(int stackWords) { return stackWords + MAXPSS; }
@@ -533,10 +539,14 @@ LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays
     // ---- PerturbPathBidir, path.cpp:1953-2160, streamed.  Light and camera sub-path share one loop so that the closest-hit
     // traversal (and the hit reconstruction behind it) is instantiated once; the connection strategies defer their shadow ray
     Contrib pc;
-    pc.camDepth = pc.lightDepth = 0;
-    pc.lsScore = pc.ssScore = 0.f;
-    pc.screenPos = V2{0.f, 0.f};
-    pc.contrib = V3{0.f, 0.f, 0.f};
+    // Stk::kTight: the connection strategies write `pc` whole, and only when they return true (dpath.h), so the zeros are needed only where no strategy
+    // succeeded -- set behind the walk, they are not nine registers carried through it
+    if constexpr (!Stk::kTight) {
+        pc.camDepth = pc.lightDepth = 0;
+        pc.lsScore = pc.ssScore = 0.f;
+        pc.screenPos = V2{0.f, 0.f};
+        pc.contrib = V3{0.f, 0.f, 0.f};
+    }
     bool ok = false;
     DeferOcclusion occ;
     {
@@ -592,6 +602,11 @@ LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays
         // every iteration = one path segment; `break` = the step's contribution is decided (ok) or the path died
         while (lightPhase || depth < camCount) {
             prof.Mark(PR_SHADE);  // the previous segment's vertex work (the first time: the sub-path head)
+            // Stk::kTight: the chain's index is made opaque to the compiler at the top of every segment.  Otherwise it computes every address the loop forms
+            // from `i` (the twelve words of the next vertex record, of the record it stores) in front of the loop and keeps them, 64 bits per lane each, alive
+            // through the traversal: 31 registers of the flagship instantiation (profiles/r14_lean_tight_vgpr_map.txt).  Formed again per segment they cost a
+            // 64-bit add each next to a memory round trip.
+            if constexpr (Stk::kTight) LMC_PIN1(i);
 #ifdef LMC_NO_VERTEX_PREFETCH  // A/B build: every vertex record but the first is fetched where it is used (twelve registers fewer across the traversal)
             DVertex sv = firstSegment ? nextV : LoadVertex(cur, N, i, lightPhase, depth);
             firstSegment = false;
@@ -714,10 +729,19 @@ LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays
         }
         StS(&prop[(size_t)PW_ENVPRIM * N + i], __int_as_float(envPrim));
     }
+    if constexpr (Stk::kTight) {
+        if (!ok) {
+            pc.camDepth = pc.lightDepth = 0;
+            pc.lsScore = pc.ssScore = 0.f;
+            pc.screenPos = V2{0.f, 0.f};
+            pc.contrib = V3{0.f, 0.f, 0.f};
+        }
+    }
     prof.Mark(PR_LOOP_EXIT);  // the last segment's vertex work: connection strategy / emitter hit
     // the one shadow ray of the step (scene.cpp:128-149), cast after its strategy has been evaluated
     if (ok && occ.pending && !LMC_EXP(P.expFlags, 1024)) ok = !Occluded(S, occ.org, occ.dir, occ.dist, stk);
     prof.Mark(PR_SHADOW);
+    if constexpr (Stk::kTight) LMC_PIN1(i);  // ... and behind the walk: the addresses of the chain's flags, contribution and Gaussian words are formed where the tail uses them
 
     // ---- proposal Gaussian + acceptance probability (mutation_mala.h:174-267)
     float a = 0.0f;

@@ -30,7 +30,7 @@ void LaunchFilmSplatProbe(const lmcd::Film &film, int n, const float *screenXY, 
 void LaunchBinsCompact(const lmcd::H2Bins &bins, const int *list, const int *listCount, int gridBlocks, hipStream_t s);
 void LaunchSplitList(const int *list, const int *listCount, int parts, int *sub, int stride, int *subCount, int gridBlocks, hipStream_t s);
 void LaunchSumF64(double *dst, const double *src, int n, hipStream_t s);  // dst[0] = sum of src[0 .. n), left to right
-void LaunchTrace(const lmcd::DScene &S, int n, const float *rays, int *prim, float *t, int anyHit, hipStream_t s);
+void LaunchTrace(const lmcd::DScene &S, int n, const float *rays, int *prim, float *t, int anyHit, bool tight, hipStream_t s);  // tight: dscene.h Stk::kTight
 void LaunchKdProbe(const lmcd::DCacheDim &C, int dim, int nq, const float *q, float radiusSq, int knn, int *outN, int *outIdx, float *outDist, hipStream_t s);
 // test probe of the lean small step's cache look-up (query_probe.hip): per query i, ints[i * LEAN_PROBE_INTS ..] = [VSource mode, nMatches, idx[5] (-1: none),
 // cacheQueries, cacheHits increments, hit of the generic CacheQuery], w[i * 5 ..] the blend weights, gauss[i * (3 dim + 1) ..] = mean, covL, invCov of
@@ -97,6 +97,13 @@ void LaunchStepSmallLeanGrad(const lmcd::DScene &S, const lmcd::DCache *cache, c
 void LaunchStepSmallPlain(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P,
                           const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads,
                           bool profile, hipStream_t s);  // one chain per thread: the grid is A.N slots; ldsStack = false: the private-stack instantiations whatever the tree
+// which instantiation of k_step_small that launch takes (step_small_plain.hip LeanFormOf)
+struct LeanForm {
+    bool lds, glossy, prof, lightless, quant, tight;
+};
+LeanForm LeanFormOf(const lmcd::DScene &S, int bvhDepth, bool glossy, bool ldsStack, bool profile);
+// what that launch asks of LDS for a tree with the given stack need (dsmall.h LeanStackWords / LeanLdsWordsPerThread): host arithmetic only
+void LeanLaunchPlan(int bvhStackNeed, int blockThreads, int *stackWords, int *ldsWordsPerThread, long long *ldsBytesPerBlock);
 // the resident schedule (step_resident.h / .hip): every chain of the slot arrays advances by up to maxSteps complete mutations in ONE launch (caches frozen);
 // lanes = active chains per 64-lane wave (16 / 32 / 64); guard[0] += chain-steps run, guard[1] += steps that would have needed the gradient program or a cache push
 void LaunchStepResident(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P, int maxSteps,

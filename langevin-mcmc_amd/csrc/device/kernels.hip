@@ -96,11 +96,13 @@ __global__ void __launch_bounds__(64) k_layout_probe(int N, int words, int mode,
         if (acc == 123456.789f) w0 += 1;  // keeps the batches ordered without changing anything
     }
 }
+// TIGHT: the walk as the three-wave lean launches run it (dscene.h Stk::kTight: a leaf's triangles two per round)
+template <bool TIGHT>
 __global__ void k_trace(DScene S, int n, const float *rays, int *prim, float *t, int anyHit) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float *r = rays + (size_t)i * 8;
         V3 org{r[0], r[1], r[2]}, dir{r[3], r[4], r[5]};
-        LocalStackT<false> stk;
+        LocalStackT<false, false, TIGHT> stk;
         if (anyHit) {
             prim[i] = BvhOccluded(S, org, dir, r[6], r[7], stk) ? 1 : 0;
         } else {
@@ -693,8 +695,10 @@ void LaunchRngProbe(int nSeeds, const unsigned long long *seeds, int mode, int n
 void LaunchLowerBoundProbe(int n, const float *cdf, int nq, const float *u, int *out, hipStream_t s) {
     hipLaunchKernelGGL(k_lower_bound_probe, dim3((nq + 63) / 64), dim3(64), 0, s, n, cdf, nq, u, out);
 }
-void LaunchTrace(const DScene &S, int n, const float *rays, int *prim, float *t, int anyHit, hipStream_t s) {
-    hipLaunchKernelGGL(k_trace, dim3(GridFor(n, 256)), dim3(256), 0, s, S, n, rays, prim, t, anyHit);
+void LaunchTrace(const DScene &S, int n, const float *rays, int *prim, float *t, int anyHit, bool tight, hipStream_t s) {
+    if (tight) hipLaunchKernelGGL(k_trace<true>, dim3(GridFor(n, 256)), dim3(256), 0, s, S, n, rays, prim, t, anyHit);
+    else
+        hipLaunchKernelGGL(k_trace<false>, dim3(GridFor(n, 256)), dim3(256), 0, s, S, n, rays, prim, t, anyHit);
 }
 void LaunchKdProbe(const DCacheDim &C, int dim, int nq, const float *q, float radiusSq, int knn, int *outN, int *outIdx, float *outDist, hipStream_t s) {
     hipLaunchKernelGGL(k_kd_probe, dim3((nq + 63) / 64), dim3(64), 0, s, C, dim, nq, q, radiusSq, knn, outN, outIdx, outDist);

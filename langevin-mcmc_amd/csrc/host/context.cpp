@@ -91,6 +91,10 @@ static void UploadScene(lmc_ctx *c) {
     }
     const lmc::Bvh4Result bvh = lmc::CollapseToBvh4(lmc::BuildSceneBvh(tris));
     c->bvhDepth = bvh.stackNeed;  // what the traversal stack must hold (the LDS stack has BVH_LDS_STACK entries)
+    for (int &h : c->leafHist) h = 0;
+    for (const lmcd::BvhNode4 &nd : bvh.nodes)
+        for (int k = 0; k < 4; k++)
+            if (nd.child[k] < 0) c->leafHist[(unsigned)~nd.child[k] & 7u]++;  // leaf code: (first << 3) | (count - 1); BVH4_EMPTY is positive
     std::vector<DMaterial> mats;
     int glossy = 0;
     for (const lmc::Material &m : sc.materials) {

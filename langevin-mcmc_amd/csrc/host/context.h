@@ -94,6 +94,7 @@ struct lmc_ctx {
     DevBuf<float> areaFunc, areaCdf, lightFunc, lightCdf, envImage, envCdfRows, envCdfCols, envRowWeights;
     DScene S;
     int bvhDepth = 0;
+    int leafHist[8] = {};  // leaves of the uploaded tree that hold 1 .. 8 triangles (lmc_lean_info)
     // film
     DevBuf<float> film, directFilm;
     // exact mode ("film_exact", INTEGRATION.md "Exact film"): the MLT splats go to filmFx, W*H*3 signed 64-bit fixed-point words (unit 2^-32) followed by

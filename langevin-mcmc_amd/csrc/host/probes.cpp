@@ -129,12 +129,17 @@ int lmc_trans_probe(int n, int mode, const float *x, const float *y, float *out)
     return 0;
     LMC_CATCH(-1)
 }
+// LMC_TRACE_TIGHT=1 (read at every call): the two ray probes walk the tree as the three-wave lean launches do (two leaf triangles per round)
+static bool TraceTight() {
+    const char *e = getenv("LMC_TRACE_TIGHT");
+    return e && atoi(e) != 0;
+}
 int lmc_trace(lmc_ctx *c, int n, const float *rays, int *prim, float *t) {
     LMC_TRY
     DevBuf<float> dR, dT;
     DevBuf<int> dP;
     dR.Upload(rays, (size_t)n * 8), dT.Alloc(n), dP.Alloc(n);
-    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 0, c->stream);
+    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 0, TraceTight(), c->stream);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(prim, dP.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(t, dT.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -146,7 +151,7 @@ int lmc_occluded(lmc_ctx *c, int n, const float *rays, int *occ) {
     DevBuf<float> dR, dT;
     DevBuf<int> dP;
     dR.Upload(rays, (size_t)n * 8), dT.Alloc(n), dP.Alloc(n);
-    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 1, c->stream);
+    LaunchTrace(c->S, n, dR.p, dP.p, dT.p, 1, TraceTight(), c->stream);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(occ, dP.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
@@ -184,6 +189,28 @@ int lmc_stream_probe(long long nWords, int reps) {
     a.Alloc((size_t)nWords), b.Alloc((size_t)nWords, false);
     for (int r = 0; r < reps; r++) LaunchStreamProbe(nWords, a.p, b.p, 0);
     HIP_CHECK(hipDeviceSynchronize());
+    return 0;
+    LMC_CATCH(-1)
+}
+// test hook, no device needed: the LDS plan of the lean small-step launch for a tree with the given stack need (device/dsmall.h)
+int lmc_lean_plan_probe(int bvhStackNeed, int blockThreads, int *stackWords, int *ldsWordsPerThread, long long *ldsBytesPerBlock) {
+    LMC_TRY
+    if (bvhStackNeed < 0 || blockThreads < 64 || !stackWords || !ldsWordsPerThread || !ldsBytesPerBlock) throw std::runtime_error("lmc_lean_plan_probe: bad arguments");
+    LeanLaunchPlan(bvhStackNeed, blockThreads, stackWords, ldsWordsPerThread, ldsBytesPerBlock);
+    return 0;
+    LMC_CATCH(-1)
+}
+// what the context's lean small-step launch is: the tree's leaves by size, its stack need and LDS stack words, the instantiation of k_step_small
+// (step_small_plain.hip LeanFormOf: the function the launch itself asks) and the block size
+int lmc_lean_info(lmc_ctx *c, int *out16) {
+    LMC_TRY
+    if (!c || !out16) throw std::runtime_error("lmc_lean_info: bad arguments");
+    for (int k = 0; k < 8; k++) out16[k] = c->leafHist[k];
+    const LeanForm f = LeanFormOf(c->S, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->profileLean);
+    int sw, wpt;
+    long long bytes;
+    LeanLaunchPlan(c->bvhDepth, c->leanBlock, &sw, &wpt, &bytes);
+    out16[8] = c->bvhDepth, out16[9] = sw, out16[10] = f.lds, out16[11] = f.glossy, out16[12] = f.lightless, out16[13] = f.quant, out16[14] = f.tight, out16[15] = c->leanBlock;
     return 0;
     LMC_CATCH(-1)
 }

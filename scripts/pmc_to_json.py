@@ -19,7 +19,8 @@ read_corr = GiB_KB / probe["FETCH_SIZE"]   # the probe reads exactly 1 GiB per l
 write_corr = GiB_KB / probe["WRITE_SIZE"]  # ... and writes 1 GiB
 # the dominant kernel of the run: the lean instantiation without light sub-paths (<true,false,false,true>) on environment-lit scenes
 # such as the headline one, the general one (<true,false,false>) otherwise
-names = [n for n in summ if n.replace(" ", "").startswith("voidk_step_small<true,false,false")]
+# (since the exact film the kernels take the film's type as their first template argument: the float film's instantiations are the ones a bench run launches)
+names = [n for n in summ if n.replace(" ", "").replace("lmcd::Film,", "").startswith("voidk_step_small<true,false,false")]
 k = summ[max(names, key=lambda n: summ[n].get("launches", 0))]
 fetch = k["FETCH_SIZE"] * 1024.0 * read_corr
 write = k["WRITE_SIZE"] * 1024.0 * write_corr
