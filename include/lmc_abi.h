@@ -446,6 +446,45 @@ int lmc_film_overflow(lmc_ctx *ctx, long long *n);
  * float film (out_fixed must be NULL).  Any output may be NULL. */
 int lmc_film_splat_probe(int W, int H, int n, const float *screen_xy, const float *rgb, int exact, long long *out_fixed, float *out_float, long long *overflow);
 
+/* ---- Chain diagnostics (device/chaindiag.hip, host/chaindiag.cpp; INTEGRATION.md "Chain diagnostics").  Opt-in; a context that uses none of it runs
+ * exactly the launches it ran before.
+ *
+ * Rows.  lmc_chain_rows gathers the rows of n chosen chains ON THE DEVICE (one wave per chain; lmc_chain_summary downloads every path buffer of
+ * every chain) and copies n * LMC_ROW_WORDS floats out.  chain_ids are GLOBAL chain ids inside this context's [chain_begin, chain_end), in any
+ * order, repeats allowed; any other id is refused (-1, a message, nothing written).  which = 0 current, 1 init states.  A row:
+ *   words  0..15  the 16 header words of lmc_chain_summary, bit for bit (and with the summary's meaning for an INVALID state: same arrays, same words)
+ *   words 16..39  pss[0..23] in GetPathPss order; the first 16 are the summary's words 16..31
+ *   word  40      the launch that ran the step which produced the state: 1 large, 2 generic small, 3 lean small, 0 the chain did not step (its
+ *                 samples are used up), -1 outside a trace
+ *   word  41      adjacentReject: 0 exactly when the chain's last step accepted its proposal
+ *   word  42      the chain's flags word (device/dchain.h F_*), as a float
+ *   words 43..47  0
+ * For which == 1 the words 40..42 are 0.
+ *
+ * Traces.  Between lmc_chain_trace_begin and _end every lock step ends by queueing the row gather of the n tracked chains on the step stream, into a
+ * device buffer of capacity_steps x n x LMC_ROW_WORDS floats: no host wait, no copy.  The row of step s is what lmc_chain_rows would return after
+ * step s, word 40 filled.  When the buffer is full further steps are not recorded but counted.  lmc_chain_trace_read waits for the step stream,
+ * copies out rows[n_steps][n][LMC_ROW_WORDS] (cap_steps, the steps `rows` has room for, must be at least the steps buffered: a smaller one is refused;
+ * rows == NULL only reports *first_step, *n_steps and *dropped and changes nothing), reports the step index of the first row
+ * (steps are counted from 1 after lmc_chains_init; after a checkpoint load from the loaded count), then empties the buffer and zeroes the drop
+ * count; recording goes on.  Every context -- a member of a group, a rank of a job -- traces its own chains.  lmc_chains_init and
+ * lmc_checkpoint_load close an open trace.
+ * While a trace is open or the step table is on, the resident schedule ("resident_steps") is not taken: a resident launch cannot be observed between
+ * its mutations, and by that schedule's contract the trajectories are the same in lock step; lmc_resident_stats shows the lock steps run.
+ * Refused (-1, a message, the context unchanged and usable): begin before lmc_chains_init or while a trace is open, n <= 0, capacity_steps <= 0, an
+ * id outside the context's range, a buffer that cannot be allocated (the message names the bytes); read / end without an open trace.
+ *
+ * Step table.  lmc_set_option "step_table" = 1 counts from the next lock step on, 0 stops counting (the table keeps its figures).  lmc_step_table copies
+ * out[3][13][13][2]: out[kind - 1][c][l][0] = chain-steps of that launch kind (1 large, 2 generic small, 3 lean small) whose chain's CURRENT state
+ * after the step has technique (c, l) = (camDepth, lightDepth); [1] = those of them whose proposal was accepted.  clear != 0 zeroes the table behind
+ * the copy.  Integer counts, exact and independent of slot order. */
+#define LMC_ROW_WORDS 48
+int lmc_chain_rows(lmc_ctx *ctx, int which, const int *chain_ids, int n, float *out);
+int lmc_chain_trace_begin(lmc_ctx *ctx, const int *chain_ids, int n, int capacity_steps);
+int lmc_chain_trace_read(lmc_ctx *ctx, float *rows, int cap_steps, long long *first_step, int *n_steps, long long *dropped);
+int lmc_chain_trace_end(lmc_ctx *ctx);
+int lmc_step_table(lmc_ctx *ctx, long long *out, int clear);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,12 @@ def lib():
             L.lmc_cache_push_probe.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]
             L.lmc_reloc_plan_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
             L.lmc_chain_slots.argtypes = [vp, vp, vp]
+        if hasattr(L, "lmc_chain_rows"):  # (an A/B library built from an older tree, LMC_LIB, has no chain diagnostics)
+            L.lmc_chain_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
+            L.lmc_chain_trace_begin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
+            L.lmc_chain_trace_read.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+            L.lmc_chain_trace_end.argtypes = [vp]
+            L.lmc_step_table.argtypes = [vp, vp, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -454,6 +460,45 @@ class Renderer:
             raise RuntimeError(_err())
         return out
 
+    # ---- chain diagnostics (include/lmc_abi.h "Chain diagnostics")
+    def chain_rows(self, ids, which=0):
+        """[n, 48] float32: the rows of the chains `ids` (GLOBAL chain ids of this renderer's range), gathered on the device; which = 0 current
+        states, 1 init states.  Words 0..15 as summary(), 16..39 pss[0..23], 40 step kind (-1 outside a trace), 41 adjacentReject, 42 flags."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.zeros((len(ids), ROW_WORDS), np.float32)
+        if lib().lmc_chain_rows(self.h, which, P(ids), len(ids), P(out)) != 0:
+            raise RuntimeError(_err())
+        return out
+
+    def trace_chains(self, ids, capacity):
+        """Open a trace of the chains `ids`: every lock step from now on records their rows on the device, up to `capacity` steps between reads."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if lib().lmc_chain_trace_begin(self.h, P(ids), len(ids), int(capacity)) != 0:
+            raise RuntimeError(_err())
+        self._trace_n = len(ids)
+
+    def trace_read(self):
+        """(first_step, dropped, rows[steps, n, 48]) of the open trace; empties the buffer, recording goes on"""
+        first, dropped, n_steps = c_ll(), c_ll(), ctypes.c_int()
+        if lib().lmc_chain_trace_read(self.h, None, 0, ctypes.byref(first), ctypes.byref(n_steps), ctypes.byref(dropped)) != 0:
+            raise RuntimeError(_err())
+        rows = np.zeros((n_steps.value, self._trace_n, ROW_WORDS), np.float32)
+        if lib().lmc_chain_trace_read(self.h, P(rows), n_steps.value, ctypes.byref(first), ctypes.byref(n_steps), ctypes.byref(dropped)) != 0:
+            raise RuntimeError(_err())
+        return first.value, dropped.value, rows
+
+    def trace_end(self):
+        if lib().lmc_chain_trace_end(self.h) != 0:
+            raise RuntimeError(_err())
+
+    def step_table(self, clear=False):
+        """int64 [3, 13, 13, 2]: [kind - 1 (large, generic small, lean small)][c][l][chain-steps | accepted], counted while
+        set_option("step_table", 1) is in force"""
+        out = np.zeros((3, 13, 13, 2), np.int64)
+        if lib().lmc_step_table(self.h, P(out), 1 if clear else 0) != 0:
+            raise RuntimeError(_err())
+        return out
+
     def step_timing(self):
         ms = ctypes.c_double()
         n = c_ll()
@@ -606,6 +651,29 @@ class Group:
         if L.lmc_group_film_reduce(self._arr, len(self.rens), ctypes.byref(ms)) != 0:
             raise RuntimeError("lmc_group_film_reduce failed: " + _err())
         return ms.value
+
+
+ROW_WORDS = 48  # include/lmc_abi.h LMC_ROW_WORDS
+TRACE_MAGIC = b"LMCTRACE"
+
+
+def trace_file_read(path):
+    """A trace file of `dpt_amd --trace-file` (little-endian: "LMCTRACE", u32 version 1, u32 row words, u32 n, u32 steps, i64 first step, n x i32
+    chain ids, steps x n x row-words float32) -> dict(ids, first_step, rows[steps, n, row_words])"""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 32 or data[:8] != TRACE_MAGIC:
+        raise ValueError("%s: not a chain trace file (magic)" % path)
+    version, words, n, steps = (int(v) for v in np.frombuffer(data, "<u4", 4, 8))
+    if version != 1:
+        raise ValueError("%s: chain trace version %d, this reader knows 1" % (path, version))
+    first = int(np.frombuffer(data, "<i8", 1, 24)[0])
+    need = 32 + 4 * n + 4 * steps * n * words
+    if len(data) != need:
+        raise ValueError("%s: %d bytes, the header asks for %d" % (path, len(data), need))
+    ids = np.frombuffer(data, "<i4", n, 32).astype(np.int32)
+    rows = np.frombuffer(data, "<f4", steps * n * words, 32 + 4 * n).astype(np.float32).reshape(steps, n, words)
+    return dict(ids=ids, first_step=first, rows=rows)
 
 
 def device_count():

@@ -187,3 +187,10 @@ void LaunchBuildCacheGrid(const float *pts, int n, int dim, int G, int m, const 
 size_t CkptRecordWords(int maxDepth, bool sampleCache, bool h2mc);
 void LaunchCkptPack(const lmcd::ChainArrays &A, int maxDepth, bool sampleCache, const float *h2Gauss, int first, int n, float *staging, hipStream_t s);
 void LaunchCkptUnpack(const lmcd::ChainArrays &A, int maxDepth, bool sampleCache, float *h2Gauss, int first, int n, const float *staging, hipStream_t s);
+// chain diagnostics (chaindiag.hip; host/chaindiag.cpp).  kindOf: one byte per rank-local CHAIN id, the launch (NEXT_*) that runs the chain's current
+// step, 0 for a chain in none of the step's work lists
+void LaunchLatchKind(const lmcd::ChainArrays &A, const int *large, const int *generic, const int *lean, const int *counts, unsigned char *kindOf, hipStream_t s);
+// n rows of 48 words (include/lmc_abi.h LMC_ROW_WORDS), one wave per row; ids: rank-local chain ids in [0, A.N); which: 0 current, 1 init; kindOf may be nullptr
+void LaunchChainRows(const lmcd::ChainArrays &A, int which, const int *ids, int n, const unsigned char *kindOf, float *out, hipStream_t s);
+// table[3][13][13][2] += the chain-steps of the step just run and those of them that were accepted, by (latched kind - 1, c, l of the state after it)
+void LaunchStepTable(const lmcd::ChainArrays &A, const unsigned char *kindOf, unsigned long long *table, hipStream_t s);

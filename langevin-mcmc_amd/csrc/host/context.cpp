@@ -332,7 +332,10 @@ lmc_ctx *lmc_create(const lmc_scene_desc *desc) {
     LMC_CATCH(nullptr)
 }
 
-void lmc_destroy(lmc_ctx *ctx) { delete ctx; }
+void lmc_destroy(lmc_ctx *ctx) {
+    if (ctx && ctx->diag) DiagFree(ctx);
+    delete ctx;
+}
 
 // HIP devices this process can use; 0 without a GPU / driver (never an error: callers use it to refuse a job they cannot place)
 int lmc_device_count(void) {
@@ -397,6 +400,9 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
             throw std::runtime_error(std::string("film_exact: this context's chains are set up with the ") + (c->filmExact ? "fixed-point" : "float") + " film; the mode is chosen before lmc_chains_init / lmc_checkpoint_load");
         c->filmExact = v != 0;
         return 0;
+    } else if (n == "step_table") {  // the per-technique step table (chaindiag.cpp): counts from the next step on
+        DiagSetStepTable(c, v != 0);
+        return 0;
     } else if (n == "resident_steps") {  // the resident schedule (RunResident); takes effect at the next lmc_chains_step
         if (o.h2mc && v > 0) throw std::runtime_error("resident_steps: H2MC contexts run in lock step only (their small step is the wave-cooperative pipeline)");
         if (v < 0 || v > 1e6) throw std::runtime_error("resident_steps: K >= 0 expected (0 = lock step)");
@@ -438,6 +444,7 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "mc_layers") *v = c->mcLayersOpt;
     else if (n == "mc_launch_streams") *v = (double)c->mcLaunchStreams;
     else if (n == "mc_launches") *v = c->mcLaunches;  // launches of the last lmc_mc_render / lmc_mc_accumulate
+    else if (n == "step_table") *v = c->diag && DiagStepTableOn(c) ? 1 : 0;
     else if (n == "resident_steps") *v = c->residentSteps;
     else if (n == "resident_lanes") *v = c->residentLanes;
     else if (n == "resident_guard") {  // steps of resident launches that would have needed the gradient program or pushed to the cache (must stay 0)
@@ -840,6 +847,7 @@ void lmc_host::SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     c->chainBegin = chainBegin;
     c->N = chainEnd - chainBegin;
     c->mutationAtInit = MutationKey(c);
+    if (c->diag) DiagChainsReset(c);
     c->perChain = perChain, c->chainsNeedExtra = chainsNeedExtra, c->stepsDone = 0, c->secondsBefore = 0;
     const size_t N = c->N;
     if (U.fromCheckpoint) c->initPath.Alloc(N * DPATH_WORDS), c->initContrib.Alloc(N * CONTRIB_WORDS), c->initScoreSum.Alloc(N);
@@ -1542,6 +1550,7 @@ bool StepPhase1(lmc_ctx *c, lmc_ctx::StepEvents &ev) {
         HIP_CHECK(hipEventRecord(ev.e[0], s));
     }
     const int cur = c->parity, nxt = 1 - c->parity;
+    if (c->diag) DiagStepBegin(c, cur);  // ahead of the fork: the relocation on the large-step stream rewrites A.chainId
     NextLists next{c->lists[nxt][0].p, c->lists[nxt][1].p, c->lists[nxt][2].p, c->listCounts[nxt].p};
     HIP_CHECK(hipMemsetAsync(c->listCounts[nxt].p, 0, 4 * sizeof(int), s));
     const int *cnt = c->listCounts[cur].p;
@@ -1661,6 +1670,7 @@ void StepPhase2(lmc_ctx *c, lmc_ctx::StepEvents &ev, bool exchanged) {
         if (!c->appliedEarly) CacheApplyLaunch(c, s);
         CacheApplyFinish(c);
     }
+    if (c->diag) DiagStepEnd(c);
     if (c->pendingResort && c->relocate) DebugResort(c);
     // the periodic full re-sort (relocate.hip): stream s is behind all of the step's launches here (StepPhase1's joins) and the next step's lists are not built yet
     if (c->relocate && c->resortEvery > 0 && c->RB.capacity >= (int)c->N && c->stepsSinceInit >= c->resortFirst && (c->stepsSinceInit - c->resortFirst) % c->resortEvery == 0) {
@@ -1754,6 +1764,9 @@ namespace {
 // last cache became ready); plain MLT never fills a cache, so its chains run resident from the first step.
 bool ResidentEligible(lmc_ctx *c) {
     if (c->residentSteps <= 0 || c->S.opt.h2mc) return false;
+    if (c->diag && DiagNeedsLockStep(c)) return false;  // a resident launch cannot be observed between its mutations
+    for (const lmc_ctx *m : c->group)                    // ... and the members of a group take the same schedule (RunSteps: they meet at barriers in lock step)
+        if (m->diag && DiagNeedsLockStep(m)) return false;
     return c->allCachesReady || !CachePending(c);
 }
 // `steps` mutations of every chain as ceil(steps / K) resident launches on the step stream, then the hand-back to lock step: the next step's work

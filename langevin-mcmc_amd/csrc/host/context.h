@@ -36,6 +36,7 @@ struct CacheDimHost {
 };
 
 int GetRcclDestroy(void *comm);  // RCCL is bound lazily (context.cpp)
+struct ChainDiag;                // chaindiag.cpp: the state of the chain diagnostics (trace buffer, kind latch, step table)
 
 }  // namespace lmc_host
 
@@ -224,6 +225,9 @@ struct lmc_ctx {
     DevBuf<unsigned long long> residentGuard;                       // [chain-steps of resident launches, steps that would have needed a gradient / push]
     bool residentResortPending = false;                             // a full re-sort is due before the next lock step (relocation on)
     int mutationAtInit = -1;  // (mala, h2mc) the resident chain state was laid out for by lmc_chains_init; lmc_chains_step refuses any other
+    // chain diagnostics (chaindiag.cpp; include/lmc_abi.h "Chain diagnostics"): nullptr until a trace is opened or "step_table" is set; owned by the
+    // context, freed by lmc_destroy (DiagFree)
+    lmc_host::ChainDiag *diag = nullptr;
     bool needGeneric = true;  // some chain may still need the generic small-step launch (gradient / deep cache tree)
     bool genericTokenOnly = false;  // ... but only as the fallback of the lean launch without light sub-paths: a few blocks, no list sort
     // init results
@@ -300,6 +304,14 @@ void PublishCacheDim(lmc_ctx *c, int d, const lmc::KdTreeResult &t, hipStream_t 
 StepParams MakeStepParams(const lmc_ctx *c);
 void BuildNextLists(lmc_ctx *c, int nxt);
 int ResidentK(const lmc_ctx *c);
+// chaindiag.cpp, for context.cpp: the hooks of the step path, each behind `if (c->diag)` at its call site
+void DiagStepBegin(lmc_ctx *c, int cur);    // head of StepPhase1, step stream: the kind latch from the work lists lists[cur]
+void DiagStepEnd(lmc_ctx *c);               // StepPhase2, behind the step's launches, ahead of the full re-sort and the list build: trace rows, step table
+bool DiagNeedsLockStep(const lmc_ctx *c);   // a trace is open or the step table is on: no resident launches
+void DiagChainsReset(lmc_ctx *c);           // SetUpChains (lmc_chains_init, lmc_checkpoint_load): closes an open trace, sizes the latch for the new chains
+void DiagSetStepTable(lmc_ctx *c, bool on);  // lmc_set_option "step_table"
+bool DiagStepTableOn(const lmc_ctx *c);
+void DiagFree(lmc_ctx *c);
 // ckpt.cpp, for mcrender.cpp (a state file of the mc film carries the same fingerprint)
 uint64_t HashSceneFiles(const lmc::Scene &sc);
 

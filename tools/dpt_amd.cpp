@@ -30,6 +30,11 @@
 // --mc-layers length|technique (mc scenes only; lmc_set_option "mc_layers", INTEGRATION.md "Layered mc film"): the render split by path length or by technique.
 // The usual EXR holds the sum of the layers; beside it every non-empty layer is written under the same name with _L<length> (two digits) or
 // _c<camDepth>_l<lightDepth> before .exr.  One device, no --checkpoint / --resume in this version.
+// Chain diagnostics (mcmc scenes on one device; include/lmc_abi.h "Chain diagnostics"): --trace-chains a,b,.. --trace-file F [--trace-steps S, default 1024]
+// records the rows of the listed chains over the first S steps of this invocation and writes F (little-endian: "LMCTRACE", u32 version 1, u32 row words,
+// u32 n, u32 steps, i64 first step, n x i32 chain ids, then steps x n x row-words floats); --step-table prints the non-empty cells of lmc_step_table,
+// one line each ("kind c l steps accepted"), before "Done!".  Either keeps the render in lock step (--resident then has no effect).
+// --help lists the flags.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -202,8 +207,73 @@ static int RenderMC(const std::string &filename, std::vector<lmc_ctx *> &ctxs, c
     return 0;
 }
 
+static std::vector<int> IntList(const std::string &list) {
+    std::vector<int> v;
+    for (size_t b = 0; b <= list.size();) {
+        const size_t e = list.find(',', b) == std::string::npos ? list.size() : list.find(',', b);
+        if (e > b) v.push_back(std::stoi(list.substr(b, e - b)));
+        b = e + 1;
+    }
+    return v;
+}
+
+// the open trace of `ctx` read and written as a trace file (layout: head of this file)
+static int WriteTrace(lmc_ctx *ctx, const std::vector<int> &ids, int capSteps, const std::string &path) {
+    const size_t n = ids.size();
+    std::vector<float> rows((size_t)capSteps * n * LMC_ROW_WORDS);
+    long long first = 0, dropped = 0;
+    int steps = 0;
+    if (lmc_chain_trace_read(ctx, rows.data(), capSteps, &first, &steps, &dropped) != 0 || lmc_chain_trace_end(ctx) != 0) {
+        fprintf(stderr, "--trace-file: %s\n", lmc_last_error());
+        return 1;
+    }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) {
+        fprintf(stderr, "--trace-file: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    const unsigned head[4] = {1u, (unsigned)LMC_ROW_WORDS, (unsigned)n, (unsigned)steps};
+    bool ok = fwrite("LMCTRACE", 1, 8, f) == 8 && fwrite(head, 4, 4, f) == 4 && fwrite(&first, 8, 1, f) == 1 && fwrite(ids.data(), 4, n, f) == n;
+    const size_t words = (size_t)steps * n * LMC_ROW_WORDS;
+    ok = ok && fwrite(rows.data(), 4, words, f) == words;
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) {
+        fprintf(stderr, "--trace-file: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    printf("Chain trace: %zu chains, steps %lld .. %lld (%lld later steps not recorded), wrote %s\n", n, first, first + steps - 1, dropped, path.c_str());
+    return 0;
+}
+
+static void PrintHelp() {
+    printf("usage: dpt_amd [flags] scene.xml ...\n"
+           "  --seedoffset N              seed offset of the render's random streams\n"
+           "  --max-derivatives-depth D   techniques longer than D get isotropic proposals (default 8)\n"
+           "  --chains N                  Markov chains resident on the GPUs (default: <dpt numchains>)\n"
+           "  --init-threads V            MLTInit streams (default 65536)\n"
+           "  --device D                  HIP device ordinal\n"
+           "  --gpus N | --devices a,b,.. shard the render over several devices\n"
+           "  --force-diffuse             every material Lambertian\n"
+           "  --maxdepth D                override <dpt maxdepth>\n"
+           "  --resident K                resident schedule: up to K mutations per launch once the caches are frozen\n"
+           "  --checkpoint FILE [--checkpoint-every S] [--max-steps S] | --resume FILE\n"
+           "  --exact-film                64-bit fixed-point film, bit-equal from run to run\n"
+           "  --spp N, --max-spp K        integrator=mc: samples per pixel / render the sample indices below K only\n"
+           "  --mc-layers length|technique   integrator=mc: the film split by path length or by technique\n"
+           "  --trace-chains a,b,..       integrator=mcmc, one device: record the rows of these chains after every step ...\n"
+           "  --trace-file FILE           ... and write them to FILE (\"LMCTRACE\", version 1; langevin-mcmc_amd trace_file_read)\n"
+           "  --trace-steps S             ... over the first S steps of this invocation (default 1024)\n"
+           "  --step-table                integrator=mcmc, one device: print chain-steps and accepted steps per launch kind and technique\n"
+           "  --help                      this text\n");
+}
+
 int main(int argc, char *argv[]) {
     if (argc <= 1) return 0;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) {
+            PrintHelp();
+            return 0;
+        }
     printf("Langevin MCMC dpt (MI355X back end)\n");
     int seedoffset = 0, device = 0, forceDiffuse = 0, maxDepth = 0, initThreads = 65536, maxDervDepth = 8, resident = 0;
     long long chains = 0, maxSteps = -1, checkpointEvery = 0;
@@ -211,6 +281,10 @@ int main(int argc, char *argv[]) {
     bool exactFilm = false;
     int mcSpp = 0, mcMaxSpp = 0;  // --spp / --max-spp (integrator = mc)
     int mcLayers = 0;              // --mc-layers length|technique (integrator = mc)
+    std::vector<int> traceChains;  // --trace-chains / --trace-file / --trace-steps, --step-table (integrator = mcmc, one device)
+    std::string traceFile;
+    int traceSteps = 1024;
+    bool traceChainsGiven = false, traceStepsGiven = false, stepTable = false;
     bool mltFlags = false;  // --chains / --resident / --init-threads given (ignored by integrator = mc)
     std::vector<int> devices;
     std::vector<std::string> filenames;
@@ -253,7 +327,24 @@ int main(int argc, char *argv[]) {
                 return 2;
             }
         }
+        else if (a == "--trace-chains") traceChains = IntList(i + 1 < argc ? argv[++i] : ""), traceChainsGiven = true;
+        else if (a == "--trace-file") traceFile = i + 1 < argc ? argv[++i] : "";
+        else if (a == "--trace-steps") traceSteps = std::stoi(argv[++i]), traceStepsGiven = true;
+        else if (a == "--step-table") stepTable = true;
         else filenames.push_back(a);
+    }
+    const bool wantTrace = traceChainsGiven || !traceFile.empty() || traceStepsGiven;
+    if (wantTrace && (traceChains.empty() || traceFile.empty())) {
+        fprintf(stderr, "--trace-chains a,b,.. and --trace-file FILE go together (--trace-steps S is optional)\n");
+        return 2;
+    }
+    if (wantTrace && traceSteps <= 0) {
+        fprintf(stderr, "--trace-steps: a positive number of steps expected\n");
+        return 2;
+    }
+    if ((wantTrace || stepTable) && devices.size() > 1) {
+        fprintf(stderr, "%s: chain diagnostics run on one device in this version (no --gpus / --devices list of more than one device)\n", wantTrace ? "--trace-chains" : "--step-table");
+        return 2;
     }
     if (devices.empty()) devices.push_back(device);
     const int visible = lmc_device_count();
@@ -280,6 +371,10 @@ int main(int argc, char *argv[]) {
         }
         lmc_ctx *ctx = ctxs[0];
         if (Opt(ctx, "integrator_mc") != 0) {  // main.cpp:92-96
+            if (wantTrace || stepTable) {
+                fprintf(stderr, "%s: %s has integrator=mc; only the Markov chains of an integrator=mcmc scene can be traced\n", wantTrace ? "--trace-chains" : "--step-table", filename.c_str());
+                return 2;
+            }
             if (mltFlags) printf("--chains / --resident / --init-threads: ignored by integrator=mc\n");
             McFlags mf;
             mf.layers = mcLayers;
@@ -383,6 +478,14 @@ int main(int argc, char *argv[]) {
         long long nContribs = 0;
         lmc_init_result(ctx, &normalization, &nContribs);
         printf("Average brightness:%g\n", normalization);
+        if (wantTrace && lmc_chain_trace_begin(ctx, traceChains.data(), (int)traceChains.size(), traceSteps) != 0) {
+            fprintf(stderr, "--trace-chains: %s\n", lmc_last_error());
+            return 1;
+        }
+        if (stepTable && lmc_set_option(ctx, "step_table", 1) != 0) {
+            fprintf(stderr, "--step-table: %s\n", lmc_last_error());
+            return 1;
+        }
         auto t0 = std::chrono::steady_clock::now();
         const long long targetSteps = (numSamplesPerChain + 1 + 63) / 64 * 64;  // calls of 64 steps; a chain that has run its samples is no longer stepped
         const long long stopAt = maxSteps >= 0 ? std::min(targetSteps, stepsDone + maxSteps) : targetSteps;
@@ -430,6 +533,21 @@ int main(int argc, char *argv[]) {
         }
         if (dropped > 0) printf("Exact film: %lld splats with a component of 2^30 or more were dropped\n", dropped);
         printf("%lld mutations, %.1f M mutations/s, wrote %s\n", mutations, mutations / elapsed * 1e-6, out.c_str());
+        if (wantTrace && WriteTrace(ctx, traceChains, traceSteps, traceFile) != 0) return 1;
+        if (stepTable) {
+            std::vector<long long> table(3 * 13 * 13 * 2);
+            if (lmc_step_table(ctx, table.data(), 0) != 0) {
+                fprintf(stderr, "--step-table: %s\n", lmc_last_error());
+                return 1;
+            }
+            printf("Step table (kind: 1 large, 2 generic small, 3 lean small): kind c l steps accepted\n");
+            for (int k = 0; k < 3; k++)
+                for (int cc = 0; cc < 13; cc++)
+                    for (int l = 0; l < 13; l++) {
+                        const long long *cell = &table[(((size_t)k * 13 + cc) * 13 + l) * 2];
+                        if (cell[0] || cell[1]) printf("%d %d %d %lld %lld\n", k + 1, cc, l, cell[0], cell[1]);
+                    }
+        }
         for (lmc_ctx *c : ctxs) lmc_destroy(c);
         printf("Done!\n");
     }
