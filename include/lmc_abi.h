@@ -393,6 +393,32 @@ int lmc_gauss_probe(int n, int dim, const float *v1, const float *M, float ss, f
  *                       and, with offset (n x dim) != NULL, px[n] = log N(-offset; mean, invCov^-1) */
 int lmc_h2_hess_probe(int c, int l, int n, const float *primary, const float *scene38, const float *vert, float *loglum, float *grad, float *hess);
 int lmc_h2_gauss_probe(int n, int dim, const float *grad, const float *hess, float sigma, const float *offset, float *gauss, float *px);
+/* Test probes of the three wave-cooperative derivative launches ON A CALLER-GIVEN WORK LIST (device/gradcoop.hip k_mala_grad, h2hess.hip k_h2_hess,
+ * h2gauss.hip k_h2_gauss; the list machinery of device/dh2coop.h; host/list_probes.cpp).  No context; device 0.  The two probes above are these with
+ * everything in one bin, in identity order.  The work list is what the kernel reads: items[n_list] = chain ids grouped by bin, count[LMC_PROBE_BINS],
+ * start[LMC_PROBE_BINS]: bin b = technique b / 8 x signature b % 8 lists items[start[b] .. start[b] + count[b]).  Refused on the host, before any device
+ * call, through lmc_last_error (which names the argument): n_list < 1 or N < n_list (n = 0 is not a call), an item outside [0, N), an item listed
+ * twice, a negative count, a bin that is not a range inside [0, n_list) or overlaps another (empty bins are not looked at), a listed chain whose (c, l)
+ * -- whose dim, for the Gaussian -- is not that of the bin's technique, grid_blocks outside [1, 4096].  All counts zero is legal (the stage with no
+ * takers): returns 0, writes nothing.  Every output is pre-filled with the float sentinel of bit pattern 0x7fc0beef, so the rows a launch wrote show.
+ *   lmc_mala_grad_list_probe  N states: primary N x 17 (time, then 2 L samples), c[N], l[N], vert N x LMC_PROBE_VERT_WORDS (the technique's 238 + 59 (c + l - 3)
+ *                             words, the rest unread), packed into the launch's records as lmc_h2_hess_probe packs them -> out N x 32 = the launch's rows:
+ *                             [0, 16) gradient (dim words written) | [16] logLum
+ *   lmc_h2_hess_list_probe    the same inputs -> out N x 288: [0, 16) gradient | [16] logLum | [32 ..) Hessian rows (stride dim; what the launch writes: the
+ *                             upper triangle and the 2 x 2 diagonal blocks)
+ *   lmc_h2_gauss_list_probe   N chains: dim[N] (even, 4 .. 16), grad N x 16, hess N x 256 (chain i's rows at stride dim[i]), flags[N] (only bit 64, F_GSEL,
+ *                             is read), offset N x 16, stage 0 or 1, sigma -> gauss 2 x N x 544 (both buffers; a listed chain's record goes to buffer
+ *                             (F_GSEL set) != (stage != 0), layout as lmc_h2_gauss_probe's), px[N] (written at stage 1 only)
+ *   lmc_coop_plan_probe       no device: for kernel 0 (k_mala_grad), 1 (k_h2_hess), 2 (k_h2_gauss) and technique index tech (0 .. 41: (c + l - 1)(c + l) / 2 - 3 + l)
+ *                             the states one task takes and the words of a state's record a wave stages (k_h2_gauss: the words of a Hessian record) */
+#define LMC_PROBE_VERT_WORDS 592
+int lmc_mala_grad_list_probe(int N, const float *primary, const int *c, const int *l, const float *vert, const float *scene38, int n_list, const int *items,
+                             const int *count, const int *start, int grid_blocks, float *out);
+int lmc_h2_hess_list_probe(int N, const float *primary, const int *c, const int *l, const float *vert, const float *scene38, int n_list, const int *items,
+                           const int *count, const int *start, int grid_blocks, float *out);
+int lmc_h2_gauss_list_probe(int N, const int *dim, const float *grad, const float *hess, const int *flags, const float *offset, int stage, float sigma, int n_list,
+                            const int *items, const int *count, const int *start, int grid_blocks, float *gauss, float *px);
+int lmc_coop_plan_probe(int kernel, int tech, int *states_per_task, int *rec_words);
 /* HBM counter calibration: `reps` launches of a kernel that reads n_words floats and writes n_words floats with the
  * chain state's access pattern (4 B per lane, SoA, unit stride).  Run under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
  * to obtain the bytes-per-count factors profiles/pmc_step_kernel.json applies.  Returns 0 on success. */

@@ -134,6 +134,12 @@ def lib():
             L.lmc_cache_push_probe.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp]
             L.lmc_reloc_plan_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
             L.lmc_chain_slots.argtypes = [vp, vp, vp]
+        if hasattr(L, "lmc_coop_plan_probe"):  # (an A/B library built from an older tree, LMC_LIB, has no work-list probes of the cooperative launches)
+            ci = ctypes.c_int
+            L.lmc_mala_grad_list_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]
+            L.lmc_h2_hess_list_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]
+            L.lmc_h2_gauss_list_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, ctypes.c_float, ci, vp, vp, vp, ci, vp, vp]
+            L.lmc_coop_plan_probe.argtypes = [ci, ci, vp, vp]
         if hasattr(L, "lmc_chain_rows"):  # (an A/B library built from an older tree, LMC_LIB, has no chain diagnostics)
             L.lmc_chain_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
             L.lmc_chain_trace_begin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
@@ -845,6 +851,63 @@ def reloc_plan_probe(step_kind, c, l, flags, placed_key, without_gaussian_only, 
     _probe("lmc_reloc_plan_probe", lib().lmc_reloc_plan_probe(n, P(sk), P(c), P(l), P(f), P(pk), 1 if without_gaussian_only else 0, int(capacity), int(skipped_before),
                                                             P(count), P(members), P(srt)))
     return count, members, srt
+
+
+# ---- test probes of the wave-cooperative derivative launches on a caller-given work list (include/lmc_abi.h; cases in tests/coop_cases.py).  Outputs are
+# float32 arrays pre-filled with PROBE_UNTOUCHED_BITS: view them as uint32 to see which rows a launch wrote.
+PROBE_VERT_WORDS = 592
+COOP_KERNELS = ("mala_grad", "h2_hess", "h2_gauss")  # the `kernel` argument of coop_plan_probe, by index
+
+
+def _work_list(items, count, start):
+    it, cnt, st = _i32(items), _i32(count), _i32(start)
+    if len(cnt) != PROBE_BINS or len(st) != PROBE_BINS:
+        raise ValueError("work list: count and start must have %d entries" % PROBE_BINS)
+    return it, cnt, st
+
+
+def _record_list_probe(name, row_words, primary, c, l, vert, scene38, items, count, start, grid_blocks):
+    pr, ve, sc = np.ascontiguousarray(primary, np.float32), np.ascontiguousarray(vert, np.float32), np.ascontiguousarray(scene38, np.float32)
+    c, l = _i32(c), _i32(l)
+    n = len(c)
+    if pr.shape != (n, 17) or ve.shape != (n, PROBE_VERT_WORDS) or len(l) != n or sc.shape != (38,):
+        raise ValueError("%s: primary must be N x 17, vert N x %d, c and l N long, scene38 38 long" % (name, PROBE_VERT_WORDS))
+    it, cnt, st = _work_list(items, count, start)
+    out = np.zeros((n, row_words), np.float32)
+    _probe(name, getattr(lib(), name)(n, P(pr), P(c), P(l), P(ve), P(sc), len(it), P(it), P(cnt), P(st), int(grid_blocks), P(out)))
+    return out
+
+
+def mala_grad_list_probe(primary, c, l, vert, scene38, items, count, start, grid_blocks):
+    """k_mala_grad over the work list (items, count[PROBE_BINS], start[PROBE_BINS]) of N states: rows [N, 32] = gradient (dim words) | .. | logLum at 16"""
+    return _record_list_probe("lmc_mala_grad_list_probe", 32, primary, c, l, vert, scene38, items, count, start, grid_blocks)
+
+
+def h2_hess_list_probe(primary, c, l, vert, scene38, items, count, start, grid_blocks):
+    """k_h2_hess over the work list of N states: rows [N, 288] = gradient | logLum at 16 | Hessian rows from 32 (stride dim)"""
+    return _record_list_probe("lmc_h2_hess_list_probe", 288, primary, c, l, vert, scene38, items, count, start, grid_blocks)
+
+
+def h2_gauss_list_probe(dim, grad, hess, flags, offset, stage, sigma, items, count, start, grid_blocks):
+    """k_h2_gauss over the work list of N chains (dim[N], grad [N, 16], hess [N, 256] at stride dim, flags[N], offset [N, 16]):
+    (gauss [2, N, 544] = both buffers, px [N])"""
+    d, f = _i32(dim), _i32(flags)
+    n = len(d)
+    g, h, o = np.ascontiguousarray(grad, np.float32), np.ascontiguousarray(hess, np.float32), np.ascontiguousarray(offset, np.float32)
+    if g.shape != (n, 16) or h.shape != (n, 256) or o.shape != (n, 16) or len(f) != n:
+        raise ValueError("h2_gauss_list_probe: grad and offset must be N x 16, hess N x 256, dim and flags N long")
+    it, cnt, st = _work_list(items, count, start)
+    gauss, px = np.zeros((2, n, 544), np.float32), np.zeros(n, np.float32)
+    _probe("lmc_h2_gauss_list_probe", lib().lmc_h2_gauss_list_probe(n, P(d), P(g), P(h), P(f), P(o), int(stage), float(sigma), len(it), P(it), P(cnt), P(st),
+                                                                  int(grid_blocks), P(gauss), P(px)))
+    return gauss, px
+
+
+def coop_plan_probe(kernel, tech):
+    """No device: (states per task, record words a wave stages per state) of COOP_KERNELS[kernel] for the technique index tech"""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _probe("lmc_coop_plan_probe", lib().lmc_coop_plan_probe(int(kernel), int(tech), ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 def comm_unique_id():

@@ -38,6 +38,31 @@ LMC_HD int H2TechDim(int t) {  // 2 * max(c + l - 1, 2)
 // lanes one state occupies in the Hessian launch: the 2 x 2 blocks of the upper triangle of a dim x dim matrix
 LMC_HD int H2BlocksOfDim(int dim) { return (dim / 2) * (dim / 2 + 1) / 2; }
 
+// The plan of a cooperative launch's tasks, one definition for the kernels and for the probes (host/list_probes.cpp lmc_coop_plan_probe):
+// a task = the states of one bin that share a wave.  A wave stages the first H2RecWordsOfTech(t) words of each state's record into LDS (the record up
+// to the end of the technique's vertParams, padded to whole 16-byte lines) and takes as many states as its lanes AND its LDS words allow.
+LMC_HD int H2RecWordsOfTech(int t) {
+    int c, l;
+    H2TechOf(t, c, l);
+    return (H2_REC_VP + 238 + 59 * (c + l - 3) + 3) & ~3;
+}
+// k_mala_grad (gradcoop.hip).  17 KB of records per wave: 13 states of dim 6 (314 words + pad), 8 of dim 12 (491).  Not more: with the task table a
+// block stays under 20 KB, so two of its waves fit a SIMD -- and one fits BESIDE a resident wave of the hot launch (256 registers, 14 KB); compiled for
+// one wave per SIMD (406 registers) the launch waited for a SIMD to drain, i.e. for the end of the hot launch (profiles/r04_fill_l_*)
+constexpr int MG_LDS_WORDS = 4352;
+LMC_HD int MalaGradStatesPerTask(int t) {  // lanes of a state: its dim / 2 Dual<2> passes
+    const int byLanes = 64 / (H2TechDim(t) / 2), byLds = MG_LDS_WORDS / H2RecWordsOfTech(t);
+    return byLanes < byLds ? byLanes : byLds;
+}
+// k_h2_hess (h2hess.hip): at most H2_HESS_LDS_WORDS floats of records per wave
+constexpr int H2_HESS_LDS_WORDS = 3328;  // 13 KB: 10 states of dim 6 (314 words + pad), 3 of dim 12 (491)
+LMC_HD int H2HessStatesPerTask(int t) {  // lanes of a state: the 2 x 2 blocks of its Hessian's triangle
+    const int byLanes = 64 / H2BlocksOfDim(H2TechDim(t)), byLds = H2_HESS_LDS_WORDS / H2RecWordsOfTech(t);
+    return byLanes < byLds ? byLanes : byLds;
+}
+// k_h2_gauss (h2gauss.hip): 16 lanes per state whatever the technique
+constexpr int H2_GAUSS_STATES_PER_TASK = 4;
+
 // Work lists of one pipeline stage: a bin holds the chains whose state of ONE technique needs its Gaussian.  A technique has H2_NSIG bins, chosen
 // by a signature of the state's materials (the BSDF type and the sampling mode of every surface vertex, hashed to three bits): the three to
 // ten states that share a wave of the Hessian launch then take the same BSDF branches as well as the same path structure (lanes active per

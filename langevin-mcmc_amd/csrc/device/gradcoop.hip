@@ -6,7 +6,8 @@
 // gradient is bit-identical to ComputeGradient's.  The state's serialised record is staged in LDS once per wave and read by broadcast.
 #ifndef LMC_NO_PF_VEC2
 #define LMC_PF_VEC2  // pathfunc.h: Dual<2> on two-wide vectors (packed FP32 instructions); per component the same operations in the same order, so the
-                     // gradient stays bit-identical to ComputeGradient's (tests/test_gpu_parity.py::test_cache_fill_pipeline_equals_the_single_launch_form)
+                     // gradient stays bit-identical to ComputeGradient's (tests/test_gpu_parity.py::test_cache_fill_pipeline_equals_the_single_launch_form on
+                     // whole chains; tests/test_gpu_coop_lists.py::test_mala_grad_rows_equal_the_per_lane_kernel_bit_for_bit state by state, on mixed work lists)
 #endif
 #include "dh2coop.h"
 #include "pathfunc.h"
@@ -42,11 +43,7 @@ __device__ __forceinline__ void GradPass(int c, int l, int b0, const float *base
 
 }  // namespace
 
-// 17 KB of records per wave: 13 states of dim 6 (314 words + pad), 8 of dim 12 (491).  Not more: with the task table a block stays under
-// 20 KB, so two of its waves fit a SIMD -- and one fits BESIDE a resident wave of the hot launch (256 registers, 14 KB); compiled for one wave
-// per SIMD (406 registers) the launch waited for a SIMD to drain, i.e. for the end of the hot launch (profiles/r04_fill_l_*)
-constexpr int MG_LDS_WORDS = 4352;
-
+// states per task and LDS words per state: dh2coop.h MalaGradStatesPerTask, H2RecWordsOfTech (MG_LDS_WORDS = 17 KB of records per wave)
 struct SceneBlock38G {  // the serialised scene block (scene.cpp:164-169) as a kernel argument: uniform, read with scalar loads
     float v[38];
 };
@@ -55,12 +52,8 @@ __global__ void __launch_bounds__(64, 2) k_mala_grad(const float *__restrict__ r
     __shared__ float lds[MG_LDS_WORDS];
     __shared__ int taskIncl[H2_NBINS];
     const int lane = threadIdx.x;
-    auto recWordsOf = [](int t) {
-        int c, l;
-        H2TechOf(t, c, l);
-        return (H2_REC_VP + 238 + 59 * (c + l - 3) + 3) & ~3;
-    };
-    auto ipwOf = [&](int t) { return min(64 / (H2TechDim(t) / 2), MG_LDS_WORDS / recWordsOf(t)); };
+    auto recWordsOf = [](int t) { return H2RecWordsOfTech(t); };
+    auto ipwOf = [](int t) { return MalaGradStatesPerTask(t); };
     const int total = H2BuildTaskTable(bins.count, taskIncl, ipwOf);
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
         const int wr = total - 1 - w;  // longest programs first

@@ -152,7 +152,8 @@ __global__ void __launch_bounds__(64) k_h2_gauss(H2Bins bins, int N, const float
     float *rc = tmp + 16, *rs = rc + 8;
     int *rp = pairTab + g * 8;
     __shared__ int taskIncl[H2_NBINS];
-    const int total = H2BuildTaskTable(bins.count, taskIncl, [](int) { return 4; });
+    static_assert(H2_GAUSS_STATES_PER_TASK == 4, "a wave's four 16-lane groups each take one state of a task");
+    const int total = H2BuildTaskTable(bins.count, taskIncl, [](int) { return H2_GAUSS_STATES_PER_TASK; });
     const float sigma = param.sigma, invSigmaSq = 1.0f / (sigma * sigma);
     for (int wk = blockIdx.x; wk < total; wk += gridDim.x) {
         const int wr = total - 1 - wk;
@@ -161,7 +162,7 @@ __global__ void __launch_bounds__(64) k_h2_gauss(H2Bins bins, int N, const float
         const int j = wr - (bin ? taskIncl[bin - 1] : 0);
         const int tCnt = bins.count[bin];
         const int n = H2TechDim(t);
-        const int first = 4 * j, nItems = min(4, tCnt - first);
+        const int first = H2_GAUSS_STATES_PER_TASK * j, nItems = min(H2_GAUSS_STATES_PER_TASK, tCnt - first);
         const bool has = g < nItems;
         const int item = has ? bins.items[bins.start[bin] + first + g] : 0;
         const bool act = has && k < n;

@@ -76,8 +76,8 @@ __device__ __forceinline__ void HessBlock(int c, int l, int dim, int bi0, int bc
 
 }  // namespace
 
-// LDS per wave: the records of the states of one task, at most H2_HESS_LDS_WORDS floats (a task takes fewer states when they do not fit)
-constexpr int H2_HESS_LDS_WORDS = 3328;  // 13 KB: 10 states of dim 6 (314 words + pad), 3 of dim 12 (491)
+// LDS per wave: the records of the states of one task, at most H2_HESS_LDS_WORDS floats (a task takes fewer states when they do not fit:
+// dh2coop.h H2HessStatesPerTask, H2RecWordsOfTech)
 
 #ifndef LMC_H2HESS_WAVES
 #define LMC_H2HESS_WAVES 1
@@ -91,12 +91,8 @@ __global__ void __launch_bounds__(64, LMC_H2HESS_WAVES) k_h2_hess(const float *_
     const int lane = threadIdx.x;
     // tasks of a bin: ceil(count / states per wave); every wave derives the same table (dh2coop.h)
     __shared__ int taskIncl[H2_NBINS];
-    auto recWordsOf = [](int t) {
-        int c, l;
-        H2TechOf(t, c, l);
-        return (H2_REC_VP + 238 + 59 * (c + l - 3) + 3) & ~3;
-    };
-    auto ipwOf = [&](int t) { return min(64 / H2BlocksOfDim(H2TechDim(t)), H2_HESS_LDS_WORDS / recWordsOf(t)); };
+    auto recWordsOf = [](int t) { return H2RecWordsOfTech(t); };
+    auto ipwOf = [](int t) { return H2HessStatesPerTask(t); };
     const int total = H2BuildTaskTable(bins.count, taskIncl, ipwOf);
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
         const int wr = total - 1 - w;  // longest programs first

@@ -3,6 +3,7 @@
 // allocates device buffers, copies the arrays in, calls the launch function of device/kernels.hip / device/relocate.hip that the renderer calls,
 // unchanged, on a stream of its own, waits and copies the results back.  The stand-in ChainArrays hold only the fields the launch reads.
 // What a launch would write out of bounds on inconsistent arguments (a list entry beyond N, a bin count that disagrees with the list) is refused here.
+// At the end: the three wave-cooperative derivative launches that CONSUME a stage's bins (k_mala_grad, k_h2_hess, k_h2_gauss) on a caller-given work list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "../../../include/lmc_abi.h"
 #include "../device/kernels.h"
 #include "../device/dh2coop.h"
+#include "../device/dh2mc.h"
 #include "hostutil.h"
 
 using namespace lmcd;
@@ -274,6 +276,152 @@ int lmc_reloc_plan_probe(int N, const unsigned char *step_kind, const int *c, co
     LaunchRelocPlan(A, 6, B, without_gaussian_only != 0, st.s);
     st.Finish();
     count.Download(out_count, 2), members.Download(out_members, N), sorted.Download(out_sorted, N);
+    return 0;
+    LMC_CATCH(-1)
+}
+
+}  // extern "C"
+
+// ---- the wave-cooperative derivative launches on a caller-given work list (device/dh2coop.h: bins, task table, grid-stride loop over the tasks)
+namespace {
+
+float Untouched() {
+    const uint32_t bits = 0x7fc0beefu;
+    float f;
+    memcpy(&f, &bits, 4);
+    return f;
+}
+
+// What the kernels trust: they index the records and the output rows by items[], and a task's LDS by the bin's technique.  fits(chain, technique):
+// the chain's state is one of that technique; techArg names the arrays that say so.  Host only: runs before the first device call.
+template <class Fits>
+void RequireWorkList(const std::string &who, int N, int n_list, const int *items, const int *count, const int *start, int grid_blocks, Fits fits, const char *techArg) {
+    auto fail = [&](const std::string &what) { throw std::runtime_error(who + ": " + what); };
+    if (n_list < 1) fail("n_list = " + std::to_string(n_list) + ": a list needs at least one entry (n = 0 is not a call)");
+    if (N < n_list) fail("N = " + std::to_string(N) + " is smaller than n_list = " + std::to_string(n_list));
+    if (!items || !count || !start) fail("items, count and start are required");
+    if (grid_blocks < 1 || grid_blocks > 4096) fail("grid_blocks = " + std::to_string(grid_blocks) + " is outside [1, 4096]");
+    std::vector<char> listed(N, 0);
+    for (int j = 0; j < n_list; j++) {
+        if (items[j] < 0 || items[j] >= N) fail("items[" + std::to_string(j) + "] = " + std::to_string(items[j]) + " is outside [0, N)");
+        if (listed[items[j]]) fail("items[" + std::to_string(j) + "] = " + std::to_string(items[j]) + " is listed twice");
+        listed[items[j]] = 1;
+    }
+    std::vector<std::pair<long long, int>> ranges;  // (start, bin) of the bins that hold something
+    for (int b = 0; b < H2_NBINS; b++) {
+        if (count[b] < 0) fail("count[" + std::to_string(b) + "] = " + std::to_string(count[b]) + " is negative");
+        if (count[b] == 0) continue;
+        if (start[b] < 0 || (long long)start[b] + count[b] > n_list)
+            fail("start[" + std::to_string(b) + "] = " + std::to_string(start[b]) + " with count " + std::to_string(count[b]) + " leaves [0, n_list)");
+        ranges.emplace_back(start[b], b);
+        for (int j = start[b]; j < start[b] + count[b]; j++)
+            if (!fits(items[j], b / H2_NSIG))
+                fail(std::string(techArg) + " of chain " + std::to_string(items[j]) + " (items[" + std::to_string(j) + "]) is not the technique of its bin " + std::to_string(b));
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t r = 1; r < ranges.size(); r++)
+        if (ranges[r - 1].first + count[ranges[r - 1].second] > ranges[r].first)
+            fail("start[" + std::to_string(ranges[r].second) + "] = " + std::to_string(start[ranges[r].second]) + " lies inside bin " + std::to_string(ranges[r - 1].second) + ": the bins overlap");
+}
+
+struct DeviceWorkList {  // items | count | start on the device, the two tables padded as the renderer's (H2_COUNT_WORDS)
+    Buf<int> items, count, start;
+    void Upload(int n_list, const int *it, const int *cnt, const int *st) {
+        std::vector<int> c(H2_COUNT_WORDS, 0), s(H2_COUNT_WORDS, 0);
+        std::copy(cnt, cnt + H2_NBINS, c.begin()), std::copy(st, st + H2_NBINS, s.begin());
+        items.Upload(it, n_list), count.Upload(c), start.Upload(s);
+    }
+    H2Bins Bins() const { return H2Bins{items.p, count.p, start.p, nullptr, nullptr}; }
+};
+
+// N serialised states (dh2coop.h `rec`): [0, 2 L + 1) primary | c | l | vertParams, the rest zero
+std::vector<float> PackRecords(int N, const float *primary, const int *c, const int *l, const float *vert) {
+    std::vector<float> rec((size_t)N * H2_REC_WORDS, 0.f);
+    for (int i = 0; i < N; i++) {
+        float *r = rec.data() + (size_t)i * H2_REC_WORDS;
+        memcpy(r + H2_REC_C, &c[i], 4), memcpy(r + H2_REC_L, &l[i], 4);
+        if (H2TechIndex(c[i], l[i]) < 0) continue;  // (cannot be listed)
+        const int L = std::max(c[i] + l[i] - 1, 2), V = 238 + 59 * (c[i] + l[i] - 3);
+        memcpy(r, primary + (size_t)i * 17, (size_t)(2 * L + 1) * sizeof(float));
+        memcpy(r + H2_REC_VP, vert + (size_t)i * LMC_PROBE_VERT_WORDS, (size_t)V * sizeof(float));
+    }
+    return rec;
+}
+
+// the body the gradient and the Hessian probe share: the launch takes (records, bins, N, scene, rows, grid, stream)
+template <class Launch>
+void RunRecordProbe(const char *who, int rowWords, Launch launch, int N, const float *primary, const int *c, const int *l, const float *vert, const float *scene38,
+                    int n_list, const int *items, const int *count, const int *start, int grid_blocks, float *out) {
+    Require(primary && c && l && vert && scene38 && out, (std::string(who) + ": primary, c, l, vert, scene38 and out are required").c_str());
+    RequireWorkList(who, N, n_list, items, count, start, grid_blocks, [&](int i, int t) { return H2TechIndex(c[i], l[i]) == t; }, "(c, l)");
+    Stream st;
+    Buf<float> dRec, dOut;
+    DeviceWorkList W;
+    dRec.Upload(PackRecords(N, primary, c, l, vert)), dOut.Fill((size_t)N * rowWords, Untouched()), W.Upload(n_list, items, count, start);
+    launch(dRec.p, W.Bins(), N, scene38, dOut.p, grid_blocks, st.s);
+    st.Finish();
+    dOut.Download(out, (size_t)N * rowWords);
+}
+
+}  // namespace
+
+static_assert(LMC_PROBE_VERT_WORDS == 238 + 59 * 6 && H2_REC_VP + LMC_PROBE_VERT_WORDS <= H2_REC_WORDS, "include/lmc_abi.h: LMC_PROBE_VERT_WORDS is the longest vertParams (dh2coop.h)");
+static_assert(MAXPSS >= 16, "the Gaussian probe lays out 16 offset words per chain");
+
+extern "C" {
+
+int lmc_mala_grad_list_probe(int N, const float *primary, const int *c, const int *l, const float *vert, const float *scene38, int n_list, const int *items,
+                             const int *count, const int *start, int grid_blocks, float *out) {
+    LMC_TRY
+    RunRecordProbe("lmc_mala_grad_list_probe", MG_OUT_WORDS, LaunchMalaGrad, N, primary, c, l, vert, scene38, n_list, items, count, start, grid_blocks, out);
+    return 0;
+    LMC_CATCH(-1)
+}
+
+int lmc_h2_hess_list_probe(int N, const float *primary, const int *c, const int *l, const float *vert, const float *scene38, int n_list, const int *items,
+                           const int *count, const int *start, int grid_blocks, float *out) {
+    LMC_TRY
+    RunRecordProbe("lmc_h2_hess_list_probe", H2_OUT_WORDS, LaunchH2Hess, N, primary, c, l, vert, scene38, n_list, items, count, start, grid_blocks, out);
+    return 0;
+    LMC_CATCH(-1)
+}
+
+int lmc_h2_gauss_list_probe(int N, const int *dim, const float *grad, const float *hess, const int *flags, const float *offset, int stage, float sigma, int n_list,
+                            const int *items, const int *count, const int *start, int grid_blocks, float *gauss, float *px) {
+    LMC_TRY
+    const std::string who = "lmc_h2_gauss_list_probe";
+    Require(dim && grad && hess && flags && offset && gauss && px, "lmc_h2_gauss_list_probe: dim, grad, hess, flags, offset, gauss and px are required");
+    Require(stage == 0 || stage == 1, "lmc_h2_gauss_list_probe: stage must be 0 or 1");
+    Require(sigma > 0.0f, "lmc_h2_gauss_list_probe: sigma must be positive");
+    for (int i = 0; i < N; i++)
+        if (dim[i] < 4 || dim[i] > 16 || (dim[i] & 1)) throw std::runtime_error(who + ": dim[" + std::to_string(i) + "] = " + std::to_string(dim[i]) + " is not even, 4 .. 16");
+    RequireWorkList(who, N, n_list, items, count, start, grid_blocks, [&](int i, int t) { return H2TechDim(t) == dim[i]; }, "dim");  // (the launch reads a technique's dim alone)
+    std::vector<float> hout((size_t)N * H2_OUT_WORDS, 0.f), off((size_t)MAXPSS * N, 0.f);
+    for (int i = 0; i < N; i++) {
+        memcpy(hout.data() + (size_t)i * H2_OUT_WORDS, grad + (size_t)i * 16, 16 * sizeof(float));
+        memcpy(hout.data() + (size_t)i * H2_OUT_WORDS + H2_OUT_HESS, hess + (size_t)i * 256, (size_t)dim[i] * dim[i] * sizeof(float));
+        for (int k = 0; k < dim[i]; k++) off[(size_t)k * N + i] = offset[(size_t)i * 16 + k];
+    }
+    Stream st;
+    Buf<float> dHout, dOff, dGauss, dPx;
+    Buf<int> dFlags;
+    DeviceWorkList W;
+    dHout.Upload(hout), dOff.Upload(off), dFlags.Upload(flags, N), W.Upload(n_list, items, count, start);
+    dGauss.Fill(2 * (size_t)N * H2_GAUSS_AOS, Untouched()), dPx.Fill(N, Untouched());
+    LaunchH2Gauss(W.Bins(), N, dHout.p, MakeH2MCParam(sigma), 0, dFlags.p, stage, dGauss.p, dOff.p, dPx.p, grid_blocks, st.s);
+    st.Finish();
+    dGauss.Download(gauss, 2 * (size_t)N * H2_GAUSS_AOS), dPx.Download(px, N);
+    return 0;
+    LMC_CATCH(-1)
+}
+
+int lmc_coop_plan_probe(int kernel, int tech, int *states_per_task, int *rec_words) {
+    LMC_TRY
+    Require(kernel >= 0 && kernel <= 2, "lmc_coop_plan_probe: kernel must be 0 (k_mala_grad), 1 (k_h2_hess) or 2 (k_h2_gauss)");
+    Require(tech >= 0 && tech < H2_NTECH, "lmc_coop_plan_probe: tech is outside [0, 42)");
+    Require(states_per_task && rec_words, "lmc_coop_plan_probe: both outputs are required");
+    *states_per_task = kernel == 0 ? MalaGradStatesPerTask(tech) : kernel == 1 ? H2HessStatesPerTask(tech) : H2_GAUSS_STATES_PER_TASK;
+    *rec_words = kernel == 2 ? H2_OUT_WORDS : H2RecWordsOfTech(tech);
     return 0;
     LMC_CATCH(-1)
 }

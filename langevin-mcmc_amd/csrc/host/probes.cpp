@@ -629,29 +629,26 @@ int lmc_h2_hess_probe(int c, int l, int n, const float *primary, const float *sc
     LMC_TRY
     const int t = H2TechIndex(c, l);
     if (t < 0) throw std::runtime_error("lmc_h2_hess_probe: technique (c,l) out of range");
-    EnsureDevice(0);
+    if (n < 1 || !primary || !vert) throw std::runtime_error("lmc_h2_hess_probe: n >= 1 states are required");
     const int L = std::max(c + l - 1, 2), V = 238 + 59 * (c + l - 3), dim = 2 * L;
-    std::vector<float> rec((size_t)n * H2_REC_WORDS, 0.f);
+    // lmc_h2_hess_list_probe (list_probes.cpp) with the simplest work list: one bin (the technique's signature 0) holds every state, in identity order
+    std::vector<float> prim17((size_t)n * 17, 0.f), vertFull((size_t)n * LMC_PROBE_VERT_WORDS, 0.f);
     for (int i = 0; i < n; i++) {
-        float *r = rec.data() + (size_t)i * H2_REC_WORDS;
-        memcpy(r, primary + (size_t)i * (2 * L + 1), (2 * L + 1) * sizeof(float));
-        memcpy(r + H2_REC_C, &c, 4), memcpy(r + H2_REC_L, &l, 4);
-        memcpy(r + H2_REC_VP, vert + (size_t)i * V, V * sizeof(float));
+        memcpy(prim17.data() + (size_t)i * 17, primary + (size_t)i * (2 * L + 1), (2 * L + 1) * sizeof(float));
+        memcpy(vertFull.data() + (size_t)i * LMC_PROBE_VERT_WORDS, vert + (size_t)i * V, V * sizeof(float));
     }
-    std::vector<int> items((size_t)n, 0), counts(2 * H2_COUNT_WORDS, 0);  // one bin holds everything: start (the second half of `counts`) is 0 everywhere
-    const int bin = t * H2_NSIG;
+    std::vector<int> cs((size_t)n, c), ls((size_t)n, l), items((size_t)n, 0), count(H2_NBINS, 0), start(H2_NBINS, 0);
     for (int i = 0; i < n; i++) items[i] = i;
-    counts[bin] = n;
-    DevBuf<float> dRec, dOut;
-    DevBuf<int> dItems, dCounts;
-    dRec.Upload(rec.data(), rec.size()), dItems.Upload(items.data(), items.size()), dCounts.Upload(counts.data(), counts.size()), dOut.Alloc((size_t)n * H2_OUT_WORDS);
-    LaunchH2Hess(dRec.p, H2Bins{dItems.p, dCounts.p, dCounts.p + H2_COUNT_WORDS, nullptr, nullptr}, n, scene38, dOut.p, 1024, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    const std::vector<float> o = dOut.Download();
+    count[t * H2_NSIG] = n;
+    std::vector<float> o((size_t)n * H2_OUT_WORDS);
+    if (lmc_h2_hess_list_probe(n, prim17.data(), cs.data(), ls.data(), vertFull.data(), scene38, n, items.data(), count.data(), start.data(), 1024, o.data()) != 0) return -1;
     for (int i = 0; i < n; i++) {
         const float *r = o.data() + (size_t)i * H2_OUT_WORDS;
         if (loglum) loglum[i] = r[H2_OUT_LOGLUM];
-        if (grad) memcpy(grad + (size_t)i * 16, r, 16 * sizeof(float));
+        if (grad) {  // the launch writes dim words
+            memset(grad + (size_t)i * 16, 0, 16 * sizeof(float));
+            memcpy(grad + (size_t)i * 16, r, dim * sizeof(float));
+        }
         if (hess) {
             float *h = hess + (size_t)i * 256;
             memset(h, 0, 256 * sizeof(float));
@@ -665,27 +662,29 @@ int lmc_h2_hess_probe(int c, int l, int n, const float *primary, const float *sc
 int lmc_h2_gauss_probe(int n, int dim, const float *grad, const float *hess, float sigma, const float *offset, float *gauss, float *px) {
     LMC_TRY
     if (dim < 4 || dim > 16 || (dim & 1)) throw std::runtime_error("lmc_h2_gauss_probe: dim must be even, 4..16");
+    if (n < 1 || !grad || !hess) throw std::runtime_error("lmc_h2_gauss_probe: n >= 1 gradients and Hessians are required");
     const int t = H2TechIndex(dim / 2 + 1, 0);
-    EnsureDevice(0);
-    std::vector<float> out((size_t)n * H2_OUT_WORDS, 0.f), off((size_t)MAXPSS * n, 0.f);
+    // lmc_h2_gauss_list_probe (list_probes.cpp) with the simplest work list: one bin holds every state, in identity order; stage 1, every flag clear
+    std::vector<float> hess256((size_t)n * 256, 0.f), off16((size_t)n * 16, 0.f);
     for (int i = 0; i < n; i++) {
-        memcpy(out.data() + (size_t)i * H2_OUT_WORDS, grad + (size_t)i * 16, 16 * sizeof(float));
-        memcpy(out.data() + (size_t)i * H2_OUT_WORDS + H2_OUT_HESS, hess + (size_t)i * dim * dim, (size_t)dim * dim * sizeof(float));
-        if (offset)
-            for (int k = 0; k < dim; k++) off[(size_t)k * n + i] = offset[(size_t)i * dim + k];
+        memcpy(hess256.data() + (size_t)i * 256, hess + (size_t)i * dim * dim, (size_t)dim * dim * sizeof(float));
+        if (offset) memcpy(off16.data() + (size_t)i * 16, offset + (size_t)i * dim, (size_t)dim * sizeof(float));
     }
-    std::vector<int> items((size_t)n, 0), counts(2 * H2_COUNT_WORDS, 0);  // one bin holds everything: start (the second half of `counts`) is 0 everywhere
-    const int bin = t * H2_NSIG;
+    std::vector<int> dims((size_t)n, dim), flags((size_t)n, 0), items((size_t)n, 0), count(H2_NBINS, 0), start(H2_NBINS, 0);
     for (int i = 0; i < n; i++) items[i] = i;
-    counts[bin] = n;
-    DevBuf<float> dOut, dOff, dGauss, dPx;
-    DevBuf<int> dItems, dCounts, dFlags;
-    dOut.Upload(out.data(), out.size()), dOff.Upload(off.data(), off.size()), dItems.Upload(items.data(), items.size()), dCounts.Upload(counts.data(), counts.size());
-    dGauss.Alloc(2 * (size_t)n * H2_GAUSS_AOS), dPx.Alloc(n), dFlags.Alloc(n);
-    LaunchH2Gauss(H2Bins{dItems.p, dCounts.p, dCounts.p + H2_COUNT_WORDS, nullptr, nullptr}, n, dOut.p, lmcd::MakeH2MCParam(sigma), 0, dFlags.p, 1, dGauss.p, dOff.p, dPx.p, 256, 0);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (gauss) HIP_CHECK(hipMemcpy(gauss, dGauss.p + (size_t)n * H2_GAUSS_AOS, (size_t)n * H2_GAUSS_AOS * sizeof(float), hipMemcpyDeviceToHost));  // stage 1 with F_GSEL clear: the second buffer
-    if (px) HIP_CHECK(hipMemcpy(px, dPx.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    count[t * H2_NSIG] = n;
+    std::vector<float> both(2 * (size_t)n * H2_GAUSS_AOS), pxAll((size_t)n);
+    if (lmc_h2_gauss_list_probe(n, dims.data(), grad, hess256.data(), flags.data(), off16.data(), 1, sigma, n, items.data(), count.data(), start.data(), 256, both.data(), pxAll.data()) != 0)
+        return -1;
+    if (gauss) {  // stage 1 with F_GSEL clear: the second buffer; the words the launch left alone (an isotropic record stores no matrices) read as zero
+        const float *g = both.data() + (size_t)n * H2_GAUSS_AOS;
+        for (size_t k = 0; k < (size_t)n * H2_GAUSS_AOS; k++) {
+            uint32_t bits;
+            memcpy(&bits, g + k, 4);
+            gauss[k] = bits == 0x7fc0beefu ? 0.0f : g[k];
+        }
+    }
+    if (px) memcpy(px, pxAll.data(), (size_t)n * sizeof(float));
     return 0;
     LMC_CATCH(-1)
 }
