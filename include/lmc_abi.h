@@ -419,6 +419,32 @@ int lmc_h2_hess_list_probe(int N, const float *primary, const int *c, const int 
 int lmc_h2_gauss_list_probe(int N, const int *dim, const float *grad, const float *hess, const int *flags, const float *offset, int stage, float sigma, int n_list,
                             const int *items, const int *count, const int *start, int grid_blocks, float *gauss, float *px);
 int lmc_coop_plan_probe(int kernel, int tech, int *states_per_task, int *rec_words);
+/* Test probe of the shading functions (device/dshade.h through device/shade_probe.hip; host/shade_probes.cpp).  No context; device 0.  One case per lane
+ * in 64-thread blocks; op 0 = EvalTex on one of a material's four texture references at st, 1 = BsdfEvaluate<G>, 2 = BsdfSample<G>, with G = (glossy != 0)
+ * the template argument the kernels are instantiated for (G = 0 runs the Lambertian functions on any record).
+ *   materials     n_mat rows of LMC_SHADE_MAT_WORDS 32-bit words in the device's record layout (device/dscene.h DMaterial):
+ *                 [type (int 0 Lambertian, 1 Phong, 2 rough dielectric) | twoSided (int) | Kd | Ks | Kt | expOrAlpha | eta | invEta | KsWeight], a texture
+ *                 reference = [bitmap (int: index into the bitmap list, -1 = constant) | value[3] | sScale | tScale].  The rows go through the packing a
+ *                 scene's materials go through (texel pool, inline texture headers).
+ *   bitmaps       bitmap_wh n_bitmaps x [W, H], bitmap_gamma[n_bitmaps], texels = the bitmaps' 3 W H floats each, back to back (n_texels floats in all)
+ *   case_ints     n x LMC_SHADE_INT_WORDS: [material index | adjoint | texture slot (0 Kd, 1 Ks, 2 Kt, 3 expOrAlpha; op 0 only)]
+ *   case_in       n x LMC_SHADE_IN_WORDS:  [wi 0..2 | normal 3..5 | wo 6..8 | st 9..10 | rnd 11..12 | uDiscrete 13 | and the values the in / out arguments
+ *                 hold going in: pdf 14 | revPdf 15 | cosWo 16 | contrib 17..19] (wo is an input of op 1 and the value going in of op 2)
+ *   out           n_rows x LMC_SHADE_OUT_WORDS: [wo 0..2 | contrib 3..5 | cosWo 6 | pdf 7 | revPdf 8] as the call left them -- a word the function did not
+ *                 write holds the bits that went in; op 0 writes the texture's value to contrib
+ *   out_ok        n_rows: BsdfSample's return value (0 / 1); 1 for op 0 and 1
+ * n_rows >= n is the length of the two outputs: both are pre-filled on the device with LMC_PROBE_SENTINEL (out_ok) and the float of bit pattern
+ * LMC_SHADE_UNTOUCHED_BITS (out), and the rows from n on must come back so.  No input may be NaN or infinite (the look-up converts st to integers).
+ * Refused on the host, before any device call, through lmc_last_error (which names the argument): an unknown op, n_mat < 1, n < 1, n_rows < n, a null
+ * pointer, a type outside 0 .. 2, a bitmap index outside [-1, n_bitmaps), a case's material index outside [0, n_mat) or (op 0) texture slot outside
+ * 0 .. 3, W or H below 1, n_texels shorter than the sum of 3 W H. */
+#define LMC_SHADE_MAT_WORDS 29
+#define LMC_SHADE_INT_WORDS 3
+#define LMC_SHADE_IN_WORDS 20
+#define LMC_SHADE_OUT_WORDS 9
+#define LMC_SHADE_UNTOUCHED_BITS 0x7fc0beefu
+int lmc_shade_probe(int op, int glossy, int n_mat, const float *materials, int n_bitmaps, const int *bitmap_wh, const float *bitmap_gamma, const float *texels,
+                    long long n_texels, int n, int n_rows, const int *case_ints, const float *case_in, int *out_ok, float *out);
 /* HBM counter calibration: `reps` launches of a kernel that reads n_words floats and writes n_words floats with the
  * chain state's access pattern (4 B per lane, SoA, unit stride).  Run under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
  * to obtain the bytes-per-count factors profiles/pmc_step_kernel.json applies.  Returns 0 on success. */

@@ -140,6 +140,9 @@ def lib():
             L.lmc_h2_hess_list_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]
             L.lmc_h2_gauss_list_probe.argtypes = [ci, vp, vp, vp, vp, vp, ci, ctypes.c_float, ci, vp, vp, vp, ci, vp, vp]
             L.lmc_coop_plan_probe.argtypes = [ci, ci, vp, vp]
+        if hasattr(L, "lmc_shade_probe"):  # (an A/B library built from an older tree, LMC_LIB, has no shading probe)
+            ci = ctypes.c_int
+            L.lmc_shade_probe.argtypes = [ci, ci, ci, vp, ci, vp, vp, vp, c_ll, ci, ci, vp, vp, vp, vp]
         if hasattr(L, "lmc_chain_rows"):  # (an A/B library built from an older tree, LMC_LIB, has no chain diagnostics)
             L.lmc_chain_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
             L.lmc_chain_trace_begin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
@@ -908,6 +911,35 @@ def coop_plan_probe(kernel, tech):
     a, b = ctypes.c_int(), ctypes.c_int()
     _probe("lmc_coop_plan_probe", lib().lmc_coop_plan_probe(int(kernel), int(tech), ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
+
+
+# ---- test probe of the texture look-up and the BSDFs (include/lmc_abi.h lmc_shade_probe; cases and references in tests/shade_cases.py, tests/shade_ref.py)
+SHADE_OPS = ("tex", "evaluate", "sample")  # the `op` argument of shade_probe, by index
+SHADE_MAT_WORDS, SHADE_INT_WORDS, SHADE_IN_WORDS, SHADE_OUT_WORDS = 29, 3, 20, 9
+
+
+def shade_probe_args(materials, bitmap_wh, bitmap_gamma, texels, case_ints, case_in):
+    """The arrays of lmc_shade_probe, contiguous and typed as the C call reads them (shared with the host build of the same source in tests/)"""
+    m = np.ascontiguousarray(materials, np.float32)
+    wh, ga, tx = _i32(bitmap_wh).reshape(-1, 2), np.ascontiguousarray(bitmap_gamma, np.float32), np.ascontiguousarray(texels, np.float32).ravel()
+    ci, cin = _i32(case_ints), np.ascontiguousarray(case_in, np.float32)
+    if m.ndim != 2 or m.shape[1] != SHADE_MAT_WORDS or len(ga) != len(wh) or ci.shape != (len(cin), SHADE_INT_WORDS) or cin.shape[1:] != (SHADE_IN_WORDS,):
+        raise ValueError("shade_probe: materials must be n_mat x %d, bitmap_wh n_bitmaps x 2, bitmap_gamma n_bitmaps, case_ints n x %d, case_in n x %d"
+                         % (SHADE_MAT_WORDS, SHADE_INT_WORDS, SHADE_IN_WORDS))
+    return m, wh, ga, tx, ci, cin
+
+
+def shade_probe(op, glossy, materials, bitmap_wh, bitmap_gamma, texels, case_ints, case_in, n=None, n_rows=None):
+    """EvalTex (op 0), BsdfEvaluate<glossy> (1) or BsdfSample<glossy> (2) of device/dshade.h, one case per lane, on the first n cases:
+    (ok int32 [n_rows], out float32 [n_rows, 9] = wo | contrib | cosWo | pdf | revPdf); rows from n on keep PROBE_SENTINEL / PROBE_UNTOUCHED_BITS"""
+    m, wh, ga, tx, ci, cin = shade_probe_args(materials, bitmap_wh, bitmap_gamma, texels, case_ints, case_in)
+    n = len(cin) if n is None else int(n)
+    n_rows = n if n_rows is None else int(n_rows)
+    if n > len(cin):
+        raise ValueError("shade_probe: n exceeds the cases given")
+    ok, out = np.zeros(max(n_rows, 1), np.int32), np.zeros((max(n_rows, 1), SHADE_OUT_WORDS), np.float32)
+    _probe("lmc_shade_probe", lib().lmc_shade_probe(int(op), int(glossy), len(m), P(m), len(wh), P(wh), P(ga), P(tx), len(tx), n, n_rows, P(ci), P(cin), P(ok), P(out)))
+    return ok, out
 
 
 def comm_unique_id():

@@ -20,6 +20,9 @@ void LaunchPluginGrad(int c, int l, const float *in, float *out, int wantGrad, h
 void LaunchPluginHess(int c, int l, const float *in, float *stage /* 655 floats of device memory */, float *out, hipStream_t s);
 void LaunchCacheProbe(const lmcd::DCache *cache, int dim, int n, const float *u, int *row, const float *query, const int *cl, float *pdf, hipStream_t s);  // step_large_cache.hip
 void LaunchTransProbe(int n, int mode, const float *x, const float *y, float *o, hipStream_t s);
+// test probe of the texture look-up and the BSDFs (shade_probe.hip, shade_probe.h: the layout of a case's ints / in / out rows): S holds materials,
+// bitmaps and texPool alone; op 0 EvalTex, 1 BsdfEvaluate<glossy>, 2 BsdfSample<glossy>; one case per lane, rows from n on are not written
+void LaunchShadeProbe(const lmcd::DScene &S, int op, bool glossy, int n, const int *ints, const float *in, int *ok, float *out, hipStream_t s);
 void LaunchStreamProbe(long long nWords, const float *in, float *out, hipStream_t s);
 void LaunchAddInto(float *dst, const float *src, size_t n, hipStream_t s);  // dst += src
 void LaunchAddIntoF64(double *dst, const double *src, size_t n, hipStream_t s);

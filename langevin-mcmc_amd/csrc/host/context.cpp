@@ -47,6 +47,58 @@ void lmc_host::EnsureDevice(int device) {
     HIP_CHECK(hipSetDevice(device));
 }
 
+// ------------------------------------------------------------------------------------------------ materials and bitmaps
+PackedMaterials lmc_host::PackMaterials(const std::vector<lmc::Material> &materials, const std::vector<lmc::Bitmap> &bitmapList) {
+    PackedMaterials pm;
+    std::vector<DMaterial> &mats = pm.mats;
+    for (const lmc::Material &m : materials) {
+        DMaterial d;
+        memset(&d, 0, sizeof(d));
+        d.type = m.type, d.twoSided = m.twoSided ? 1 : 0;
+        auto tex = [](const lmc::TextureRef &t) {
+            DTexRef r;
+            r.bitmap = t.bitmap, r.sScale = t.sScale, r.tScale = t.tScale;
+            memcpy(r.value, t.value, 12);
+            return r;
+        };
+        d.Kd = tex(m.Kd), d.Ks = tex(m.Ks), d.Kt = tex(m.Kt), d.expOrAlpha = tex(m.expOrAlpha);
+        d.eta = m.eta, d.invEta = m.invEta, d.KsWeight = m.KsWeight;
+        if (m.type != lmc::BSDF_LAMBERTIAN && m.type != lmc::BSDF_PHONG && m.type != lmc::BSDF_ROUGHDIELECTRIC) throw std::runtime_error("unknown BSDF type");
+        if (m.type != lmc::BSDF_LAMBERTIAN) pm.glossy = 1;
+        for (const DTexRef *r : {&d.Kd, &d.Ks, &d.Kt, &d.expOrAlpha})
+            if (r->bitmap >= (int)bitmapList.size()) throw std::runtime_error("a texture names a bitmap the scene does not have");
+        mats.push_back(d);
+    }
+    // every bitmap's texels in ONE buffer (DScene::texPool): a textured DTexRef names its bitmap by the word offset of its texels there and carries
+    // width / height / gamma itself (dscene.h LMC_TEX_INLINE), so that a look-up needs no header fetch between the material record and the texels
+    std::vector<float> &pool = pm.pool;
+    std::vector<size_t> &poolOff = pm.poolOff;
+    for (const lmc::Bitmap &bm : bitmapList) {
+        poolOff.push_back(pool.size());
+        pool.insert(pool.end(), bm.img.data.begin(), bm.img.data.end());
+    }
+    if (pool.size() >= (size_t)1 << 31) throw std::runtime_error("the scene's bitmaps hold more than 2^31 words");
+    if (pool.empty()) pool.push_back(0.f);
+#if LMC_TEX_INLINE
+    for (DMaterial &d : mats)
+        for (DTexRef *r : {&d.Kd, &d.Ks, &d.Kt, &d.expOrAlpha})
+            if (r->bitmap >= 0) {
+                const lmc::Bitmap &bm = bitmapList[r->bitmap];
+                const int W = bm.img.width, H = bm.img.height;
+                r->bitmap = (int)poolOff[r->bitmap];
+                memcpy(&r->value[0], &W, 4), memcpy(&r->value[1], &H, 4), r->value[2] = bm.gamma;
+            }
+#endif
+    return pm;
+}
+
+std::vector<DBitmap> lmc_host::BitmapHeaders(const PackedMaterials &pm, const std::vector<lmc::Bitmap> &bitmapList, const float *devPool) {
+    std::vector<DBitmap> bitmaps;
+    for (size_t i = 0; i < bitmapList.size(); i++) bitmaps.push_back(DBitmap{devPool + pm.poolOff[i], bitmapList[i].img.width, bitmapList[i].img.height, bitmapList[i].gamma});
+    if (bitmaps.empty()) bitmaps.push_back(DBitmap{nullptr, 0, 0, 1.f});
+    return bitmaps;
+}
+
 // ------------------------------------------------------------------------------------------------ scene upload
 static void UploadScene(lmc_ctx *c) {
     const lmc::Scene &sc = *c->scene;
@@ -95,49 +147,12 @@ static void UploadScene(lmc_ctx *c) {
     for (const lmcd::BvhNode4 &nd : bvh.nodes)
         for (int k = 0; k < 4; k++)
             if (nd.child[k] < 0) c->leafHist[(unsigned)~nd.child[k] & 7u]++;  // leaf code: (first << 3) | (count - 1); BVH4_EMPTY is positive
-    std::vector<DMaterial> mats;
-    int glossy = 0;
-    for (const lmc::Material &m : sc.materials) {
-        DMaterial d;
-        memset(&d, 0, sizeof(d));
-        d.type = m.type, d.twoSided = m.twoSided ? 1 : 0;
-        auto tex = [](const lmc::TextureRef &t) {
-            DTexRef r;
-            r.bitmap = t.bitmap, r.sScale = t.sScale, r.tScale = t.tScale;
-            memcpy(r.value, t.value, 12);
-            return r;
-        };
-        d.Kd = tex(m.Kd), d.Ks = tex(m.Ks), d.Kt = tex(m.Kt), d.expOrAlpha = tex(m.expOrAlpha);
-        d.eta = m.eta, d.invEta = m.invEta, d.KsWeight = m.KsWeight;
-        if (m.type != lmc::BSDF_LAMBERTIAN && m.type != lmc::BSDF_PHONG && m.type != lmc::BSDF_ROUGHDIELECTRIC) throw std::runtime_error("unknown BSDF type");
-        if (m.type != lmc::BSDF_LAMBERTIAN) glossy = 1;
-        mats.push_back(d);
-    }
-    // every bitmap's texels in ONE buffer (DScene::texPool): a textured DTexRef names its bitmap by the word offset of its texels there and carries
-    // width / height / gamma itself (dscene.h LMC_TEX_INLINE), so that a look-up needs no header fetch between the material record and the texels
-    std::vector<DBitmap> bitmaps;
-    std::vector<float> pool;
-    std::vector<size_t> poolOff;
-    for (const lmc::Bitmap &bm : sc.bitmaps) {
-        poolOff.push_back(pool.size());
-        pool.insert(pool.end(), bm.img.data.begin(), bm.img.data.end());
-    }
-    if (pool.size() >= (size_t)1 << 31) throw std::runtime_error("the scene's bitmaps hold more than 2^31 words");
-    if (pool.empty()) pool.push_back(0.f);
-    c->texPool.Upload(pool);
-    for (size_t i = 0; i < sc.bitmaps.size(); i++) bitmaps.push_back(DBitmap{c->texPool.p + poolOff[i], sc.bitmaps[i].img.width, sc.bitmaps[i].img.height, sc.bitmaps[i].gamma});
-    if (bitmaps.empty()) bitmaps.push_back(DBitmap{nullptr, 0, 0, 1.f});
-    c->bitmaps.Upload(bitmaps);
-#if LMC_TEX_INLINE
-    for (DMaterial &d : mats)
-        for (DTexRef *r : {&d.Kd, &d.Ks, &d.Kt, &d.expOrAlpha})
-            if (r->bitmap >= 0) {
-                const lmc::Bitmap &bm = sc.bitmaps[r->bitmap];
-                const int W = bm.img.width, H = bm.img.height;
-                r->bitmap = (int)poolOff[r->bitmap];
-                memcpy(&r->value[0], &W, 4), memcpy(&r->value[1], &H, 4), r->value[2] = bm.gamma;
-            }
-#endif
+    // the material records and every bitmap's texels in ONE buffer (DScene::texPool): PackMaterials above
+    const PackedMaterials pm = PackMaterials(sc.materials, sc.bitmaps);
+    const std::vector<DMaterial> &mats = pm.mats;
+    const int glossy = pm.glossy;
+    c->texPool.Upload(pm.pool);
+    c->bitmaps.Upload(BitmapHeaders(pm, sc.bitmaps, c->texPool.p));
     std::vector<DLight> lights;
     for (const lmc::Light &L : sc.lights) {
         DLight d;

@@ -295,6 +295,19 @@ struct ChainSetUp {
     bool fromCheckpoint = false;  // the init states and the chains' words come from records (checkpoint.hip) instead of the init-state regeneration
 };
 
+// The material records and the bitmaps as the device reads them: what UploadScene (context.cpp) puts into DScene::materials / texPool / bitmaps, and
+// what the shading probe (shade_probes.cpp) looks its textures up through.  `mats` are final -- with LMC_TEX_INLINE a textured reference already names
+// its texels' word offset in `pool` and carries width / height / gamma --, `pool` holds at least one word.
+struct PackedMaterials {
+    std::vector<DMaterial> mats;
+    std::vector<float> pool;
+    std::vector<size_t> poolOff;  // first word of every bitmap in `pool`
+    int glossy = 0;               // any non-Lambertian record
+};
+PackedMaterials PackMaterials(const std::vector<lmc::Material> &materials, const std::vector<lmc::Bitmap> &bitmaps);
+// DScene::bitmaps for a pool that lives at devPool (at least one entry)
+std::vector<DBitmap> BitmapHeaders(const PackedMaterials &pm, const std::vector<lmc::Bitmap> &bitmaps, const float *devPool);
+
 // context.cpp, for ckpt.cpp (a load sets the chains up, publishes the cache dims its file holds ready and builds the next step's lists) and mcrender.cpp
 void SetUpChains(lmc_ctx *c, const ChainSetUp &U);
 void GroupSetUpMerge(const std::vector<lmc_ctx *> &g);
