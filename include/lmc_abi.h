@@ -536,6 +536,47 @@ int lmc_chain_trace_begin(lmc_ctx *ctx, const int *chain_ids, int n, int capacit
 int lmc_chain_trace_read(lmc_ctx *ctx, float *rows, int cap_steps, long long *first_step, int *n_steps, long long *dropped);
 int lmc_chain_trace_end(lmc_ctx *ctx);
 int lmc_step_table(lmc_ctx *ctx, long long *out, int clear);
+/* Pending splat lists.  lmc_chain_splats gathers, on the device, the pending splat list of n chosen chains -- the contributions a rejected (or partly
+ * accepted) step splats again, the list row word 15 only counts.  chain_ids follow the rules of lmc_chain_rows.  counts[k] = the length of chain k's list;
+ * out[(k * cap + e) * LMC_SPLAT_WORDS ..] = x, y (screen position in [0,1)^2), r, g, b (the values as stored: scaled, not yet weighted by the acceptance)
+ * and the entry's label c * 16 + l as a float, -1 when "film_layers" is off; e < min(counts[k], cap), the entries behind are zero.  cap = 1 ..
+ * LMC_SPLAT_MAX_ENTRIES.  Of an INVALID state the list means nothing (the chain loop does not splat it). */
+#define LMC_SPLAT_WORDS 6
+#define LMC_SPLAT_MAX_ENTRIES 85
+int lmc_chain_splats(lmc_ctx *ctx, const int *chain_ids, int n, int cap, float *out, int *counts);
+
+/* ---- Layered MLT film (INTEGRATION.md "Layered MLT film"; device/dchain.h ChainFilmLayers, device/step_*_layers.hip, host/filmlayers.cpp).
+ * lmc_set_option "film_layers" = 1 (by path length) or 2 (by technique), default 0 (off: the films and the kernels above).  The option follows the rules of
+ * "film_exact": set BEFORE the context's first lmc_chains_init, kept for life, a change on a context whose chains are set up is refused (-1, the context
+ * stays usable).  Exact mode only: with "film_layers" set and "film_exact" = 0 lmc_chains_init returns -1 with a message naming both options.
+ *   the film     n_layers exact films of W*H*3 int64 words one after the other and ONE overflow word.  Every splat of the chain loop goes to the layer of
+ *                its contribution's technique (c, l) = (camDepth, lightDepth); pixel, finite and range rules per contribution are those of the exact
+ *                film, so the layers sum to the unlayered exact film WORD FOR WORD, with the same chain states and counters.
+ *   numbering    that of "mc_layers" (above): D = maxdepth (1 .. 12); 1: D layers, layer L - 1; 2: D (D + 3) / 2 layers, layer (L - 1)(L + 2) / 2 + l.
+ *                A technique outside the table is dropped whole and counted in the overflow word, never written.
+ *   labels       the techniques of the pending splat lists live in one byte c * 16 + l per entry, indexed by chain id (lmc_chain_splats reads them)
+ *   the total    lmc_film_read, lmc_film_read_fixed, lmc_film_overflow and lmc_film_device_ptr apply to the sum of the layers (int64 adds), made when
+ *                they are called: a caller that ignores the layers sees the unlayered exact film, the same words
+ *   lmc_film_layer_info        *mode, *n_layers of the film the context holds (n_layers = 0: unlayered); cl receives at most cap pairs, (L, -1) in length
+ *                              mode, (c, l) in technique mode
+ *   lmc_film_read_layer        one layer as W*H*3 floats, converted like lmc_film_read and un-normalised
+ *   lmc_film_read_layer_fixed  one layer's raw words
+ *   lmc_film_clear             zeroes every layer and the counter
+ *   lmc_group_film_reduce      sums the members' films layer by layer (and the overflow words); all members must have the same mode: a mixed group is
+ *                              refused by lmc_group_chains_init and lmc_group_film_reduce, as a mixed "film_exact" is
+ * While the mode is on the resident schedule ("resident_steps") is not taken, exactly as while a trace is open: by that schedule's contract the
+ * trajectories are the same in lock step; lmc_resident_stats shows the lock steps run.
+ * Refused in this version (-1, a message naming film_layers, nothing written, the context usable): H2MC contexts (at lmc_chains_init), lmc_checkpoint_save /
+ * _load and their group forms, lmc_film_allreduce on a communicator of more than one rank, a layer index outside [0, n_layers), the layer readers on an
+ * unlayered context.
+ * lmc_film_layer_splat_probe (test probe): n splats (screen_xy n x 2, rgb n x 3, techniques cl n x 2 = camDepth, lightDepth) through the device's layered
+ * splat routine into a fresh W x H film of mode / D.  out_fixed: n_layers * W*H*3 words; *overflow: the film's overflow word (range rule AND outside the
+ * table); *outside: the finite splats whose technique is outside the table.  Any output may be NULL. */
+int lmc_film_layer_info(lmc_ctx *ctx, int *mode, int *n_layers, int *cl, int cap);
+int lmc_film_read_layer(lmc_ctx *ctx, int layer, float *rgb);
+int lmc_film_read_layer_fixed(lmc_ctx *ctx, int layer, long long *words);
+int lmc_film_layer_splat_probe(int W, int H, int mode, int D, int n, const float *screen_xy, const float *rgb, const int *cl, long long *out_fixed, long long *overflow,
+                               long long *outside);
 
 #ifdef __cplusplus
 }

@@ -149,12 +149,40 @@ def lib():
             L.lmc_chain_trace_read.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
             L.lmc_chain_trace_end.argtypes = [vp]
             L.lmc_step_table.argtypes = [vp, vp, ctypes.c_int]
+        if hasattr(L, "lmc_film_layer_info"):  # (an A/B library built from an older tree, LMC_LIB, has no layered MLT film)
+            ci = ctypes.c_int
+            L.lmc_film_layer_info.argtypes = [vp, vp, vp, vp, ci]
+            L.lmc_film_read_layer.argtypes = [vp, ci, vp]
+            L.lmc_film_read_layer_fixed.argtypes = [vp, ci, vp]
+            L.lmc_chain_splats.argtypes = [vp, vp, ci, ci, vp, vp]
+            L.lmc_film_layer_splat_probe.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
 
 def _err():
     return lib().lmc_last_error().decode()
+
+
+SPLAT_WORDS, SPLAT_MAX_ENTRIES = 6, 85  # include/lmc_abi.h LMC_SPLAT_WORDS, LMC_SPLAT_MAX_ENTRIES
+
+
+def film_layer_of(mode, c, l):
+    """The layer of technique (c, l) = (camDepth, lightDepth) in a layered film ("mc_layers" and "film_layers" share the numbering): mode 1 (by
+    path length L = c + l - 1) L - 1, mode 2 (by technique) (L - 1)(L + 2) / 2 + l; -1: no such technique.  A film of maxdepth D holds the layers below
+    film_layer_count(mode, D)."""
+    L = c + l - 1
+    if mode not in (1, 2):
+        raise ValueError("film_layer_of: mode is 1 (by path length) or 2 (by technique)")
+    if c < 1 or l < 0 or L < 1:
+        return -1
+    return L - 1 if mode == 1 else (L - 1) * (L + 2) // 2 + l
+
+
+def film_layer_count(mode, max_depth):
+    if mode not in (0, 1, 2):
+        raise ValueError("film_layer_count: mode is 0 (off), 1 (by path length) or 2 (by technique)")
+    return 0 if mode == 0 else max_depth if mode == 1 else max_depth * (max_depth + 3) // 2
 
 
 class Renderer:
@@ -237,6 +265,11 @@ class Renderer:
         if lib().lmc_film_read(self.h, P(f)) != 0:
             raise RuntimeError(_err())
         return f
+
+    def film_clear(self):
+        """zeroes the film (exact mode: the words and the overflow counter; "film_layers": every layer); the chains go on from where they are"""
+        if lib().lmc_film_clear(self.h) != 0:
+            raise RuntimeError(_err())
 
     def film_fixed(self):
         """Exact mode (set_option("film_exact", 1) before init_chains / load_checkpoint): the film's raw words, int64 [H, W, 3], one unit =
@@ -500,6 +533,59 @@ class Renderer:
         if lib().lmc_chain_trace_end(self.h) != 0:
             raise RuntimeError(_err())
 
+    def chain_splats(self, ids, cap=SPLAT_MAX_ENTRIES):
+        """(counts[n] int32, entries[n, cap, 6] float32): the pending splat lists of the chains `ids` (GLOBAL chain ids of this renderer's range),
+        gathered on the device.  An entry: x, y, r, g, b as stored and its label camDepth * 16 + lightDepth (-1 unless "film_layers" is set);
+        entries from min(counts[k], cap) on are zero."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        cap = int(cap)
+        if len(ids) == 0:
+            raise ValueError("chain_splats: at least one chain id expected")
+        if not 1 <= cap <= SPLAT_MAX_ENTRIES:
+            raise ValueError("chain_splats: cap is 1 .. %d entries per chain" % SPLAT_MAX_ENTRIES)
+        out = np.zeros((len(ids), cap, SPLAT_WORDS), np.float32)
+        counts = np.zeros(len(ids), np.int32)
+        if lib().lmc_chain_splats(self.h, P(ids), len(ids), cap, P(out), P(counts)) != 0:
+            raise RuntimeError(_err())
+        return counts, out
+
+    # ---- the layered MLT film (set_option("film_layers", 1 | 2) and ("film_exact", 1) before init_chains; include/lmc_abi.h "Layered MLT film")
+    def film_layer_info(self):
+        """(mode, layers) of the MLT film the renderer holds: mode 0 / 1 (by path length) / 2 (by technique), layers a list of (L, -1) in length
+        mode and of (camDepth, lightDepth) in technique mode, [] for an unlayered film"""
+        mode, n = ctypes.c_int(), ctypes.c_int()
+        if lib().lmc_film_layer_info(self.h, ctypes.byref(mode), ctypes.byref(n), None, 0) != 0:
+            raise RuntimeError(_err())
+        cl = (ctypes.c_int * (2 * max(n.value, 1)))()
+        if lib().lmc_film_layer_info(self.h, ctypes.byref(mode), ctypes.byref(n), cl, n.value) != 0:
+            raise RuntimeError(_err())
+        return mode.value, [(int(cl[2 * k]), int(cl[2 * k + 1])) for k in range(n.value)]
+
+    def film_layer(self, k):
+        """layer k of the layered MLT film as film() returns the whole, float32 [H, W, 3], un-normalised"""
+        if int(k) != k:
+            raise TypeError("film_layer: an integer layer index expected")
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        if lib().lmc_film_read_layer(self.h, int(k), P(out)) != 0:
+            raise RuntimeError("lmc_film_read_layer failed: " + _err())
+        return out
+
+    def film_layer_fixed(self, k):
+        """layer k's raw words, int64 [H, W, 3]"""
+        if int(k) != k:
+            raise TypeError("film_layer_fixed: an integer layer index expected")
+        f = np.zeros((self.height, self.width, 3), np.int64)
+        if lib().lmc_film_read_layer_fixed(self.h, int(k), P(f)) != 0:
+            raise RuntimeError("lmc_film_read_layer_fixed failed: " + _err())
+        return f
+
+    def film_layers_fixed(self):
+        """every layer's raw words, int64 [n, H, W, 3]; their sum over the first axis is film_fixed()"""
+        n = len(self.film_layer_info()[1])
+        if n == 0:
+            raise RuntimeError("film_layers_fixed: the renderer holds no layered film (set_option(\"film_layers\", 1 or 2) and (\"film_exact\", 1) before init_chains)")
+        return np.stack([self.film_layer_fixed(k) for k in range(n)])
+
     def step_table(self, clear=False):
         """int64 [3, 13, 13, 2]: [kind - 1 (large, generic small, lean small)][c][l][chain-steps | accepted], counted while
         set_option("step_table", 1) is in force"""
@@ -573,6 +659,9 @@ class Group:
         modes = [int(r.get_option("film_exact")) for r in self.rens]
         if len(set(modes)) > 1:
             raise RuntimeError("Group: the members differ in film_exact (%s); a group's films are merged in one format" % modes)
+        layers = [int(r.get_option("film_layers")) if hasattr(lib(), "lmc_film_layer_info") else 0 for r in self.rens]
+        if len(set(layers)) > 1:
+            raise RuntimeError("Group: the members differ in film_layers (%s); a group's films are merged layer by layer" % layers)
 
     def film_overflow(self):
         """film_overflow() of the members summed (after film_reduce(): still each member's own count)"""
@@ -746,6 +835,22 @@ def mc_chunks_probe(begin, end, n_tiles, launch_streams):
     o = np.zeros((max(n, 1), 2), np.int64)
     lib().lmc_mc_chunks_probe(int(begin), int(end), int(n_tiles), int(launch_streams), P(o), n)
     return [tuple(int(v) for v in r) for r in o[:n]]
+
+
+def film_layer_splat_probe(width, height, mode, max_depth, screen_xy, rgb, cl):
+    """Test probe: the splats (screen_xy [n, 2], rgb [n, 3], techniques cl [n, 2] = camDepth, lightDepth) through the device's layered splat routine
+    into a fresh film.  Returns (words int64 [n_layers, H, W, 3], overflow word, splats outside the table)."""
+    xy = np.ascontiguousarray(screen_xy, np.float32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(cl, np.int32).reshape(-1, 2)
+    if not (len(xy) == len(c) == len(t)):
+        raise ValueError("film_layer_splat_probe: screen_xy, rgb and cl differ in length")
+    n_layers = film_layer_count(mode, max_depth)
+    out = np.zeros((max(n_layers, 1), height, width, 3), np.int64)
+    ovf, outside = c_ll(), c_ll()
+    if lib().lmc_film_layer_splat_probe(width, height, mode, max_depth, len(xy), P(xy), P(c), P(t), P(out), ctypes.byref(ovf), ctypes.byref(outside)) != 0:
+        raise RuntimeError("lmc_film_layer_splat_probe failed: " + _err())
+    return out[:n_layers], int(ovf.value), int(outside.value)
 
 
 def film_splat_probe(width, height, screen_xy, rgb, exact=True):

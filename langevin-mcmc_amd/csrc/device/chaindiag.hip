@@ -139,11 +139,34 @@ __global__ void __launch_bounds__(256) k_step_table(ChainArrays A, const unsigne
     }
 }
 
+// The pending splat lists of n chosen chains (lmc_chain_splats), one lane per chain: counts[j] = the list length of chain ids[j] (through A.slotOf),
+// out[(j * cap + k) * 6 ..] = x, y, r, g, b of entry k as stored and its label c * 16 + l (labels: the layered film's array, by chain id; nullptr: -1).
+// Entries from min(length, cap) on are not written.  ids: rank-local chain ids in [0, N), checked by the host.
+__global__ void __launch_bounds__(64) k_chain_splats(ChainArrays A, const unsigned char *labels, const int *ids, int n, int cap, float *out, int *counts) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int chain = ids[j];
+    const int i = A.slotOf ? A.slotOf[chain] : chain;
+    const size_t N = A.N;
+    const int len = A.curSplatCount[i];
+    counts[j] = len;
+    const int m = len < cap ? (len < 0 ? 0 : len) : cap;
+    for (int k = 0; k < m; k++) {
+        float *o = out + ((size_t)j * cap + k) * 6;
+        for (int w = 0; w < SPLAT_WORDS; w++) o[w] = A.curSplat[((size_t)k * SPLAT_WORDS + w) * N + i];
+        o[5] = labels ? (float)labels[(size_t)k * N + chain] : -1.0f;
+    }
+}
+
 }  // namespace
 }  // namespace lmcd
 
 using namespace lmcd;
 
+void LaunchChainSplats(const ChainArrays &A, const unsigned char *labels, const int *ids, int n, int cap, float *out, int *counts, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_chain_splats, dim3((n + 63) / 64), dim3(64), 0, s, A, labels, ids, n, cap, out, counts);
+}
 void LaunchLatchKind(const ChainArrays &A, const int *large, const int *generic, const int *lean, const int *counts, unsigned char *kindOf, hipStream_t s) {
     if (A.N <= 0) return;
     (void)hipMemsetAsync(kindOf, 0, (size_t)A.N, s);  // a chain in no list does not step

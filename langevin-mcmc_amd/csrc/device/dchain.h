@@ -341,6 +341,68 @@ LMC_D void Splat(const FilmFixed &film, V2 screenPos, V3 contrib) {
     }
 }
 
+// The layer of technique (c, l) = (camDepth, lightDepth), path length L = c + l - 1 >= 1.  Mode 1 (by length): L - 1.  Mode 2 (by technique): the
+// lengths one after the other, length L with its L + 1 techniques l = 0 .. L: (L - 1)(L + 2) / 2 + l.  -1: no such technique.  With D = maxdepth a
+// film has McLayerCount layers, and a technique belongs to the table when its layer is below that.  ("mc_layers" and "film_layers" share the numbering.)
+LMC_HD int McLayerOf(int mode, int c, int l) {
+    const int L = c + l - 1;
+    if (c < 1 || l < 0 || L < 1) return -1;
+    return mode == 1 ? L - 1 : (L - 1) * (L + 2) / 2 + l;
+}
+LMC_HD int McLayerCount(int mode, int maxDepth) { return mode == 1 ? maxDepth : mode == 2 ? maxDepth * (maxDepth + 3) / 2 : 0; }
+
+// The layered MLT film ("film_layers", INTEGRATION.md "Layered MLT film"): nLayers exact films of W*H*3 words one after the other, ONE overflow word behind
+// the last.  A third film TYPE: only the translation units step_*_layers.hip instantiate the step kernels with it, DispatchFilm never yields it, so the
+// kernels of the other two types hold no trace of it.  A contribution goes to the layer McLayerOf gives its technique; the techniques of a chain's pending
+// splat list (A.curSplat) live in `labels`, one byte c * 16 + l per entry, entry k of the chain with rank-local id `id` at labels[k * N + id] -- by CHAIN
+// id, not by slot, so that relocation and the full re-sort (relocate.hip) move nothing of it.
+struct ChainFilmLayers {
+    unsigned long long *fx;  // nLayers * W*H*3 + 1
+    unsigned char *labels;   // MAXCONTRIB x N
+    int W, H, nLayers, mode;
+};
+template <class FILM>
+struct FilmIsLayered {
+    static constexpr bool value = false;
+};
+template <>
+struct FilmIsLayered<ChainFilmLayers> {
+    static constexpr bool value = true;
+};
+// What the splat sites of the chain loop call.  Float and exact film: Splat, the technique unused.
+LMC_D void SplatT(const Film &film, V2 screenPos, V3 contrib, int, int) { Splat(film, screenPos, contrib); }
+LMC_D void SplatT(const FilmFixed &film, V2 screenPos, V3 contrib, int, int) { Splat(film, screenPos, contrib); }
+// ... layered: Splat(FilmFixed)'s pixel, finite and range rules per contribution; a technique outside the table is dropped whole and counted in the
+// overflow word like a component out of range, never written
+LMC_D void SplatT(const ChainFilmLayers &film, V2 screenPos, V3 contrib, int camDepth, int lightDepth) {
+    int ix = Clampi((int)(screenPos.x * film.W), 0, film.W - 1);
+    int iy = Clampi((int)(screenPos.y * film.H), 0, film.H - 1);
+    if (AllFinite(contrib)) {
+        const int layer = McLayerOf(film.mode, camDepth, lightDepth);
+        const size_t words = (size_t)film.W * film.H * 3;
+        if (fabsf(contrib.x) >= FILM_FX_LIMIT || fabsf(contrib.y) >= FILM_FX_LIMIT || fabsf(contrib.z) >= FILM_FX_LIMIT || layer < 0 || layer >= film.nLayers) {
+            atomicAdd(film.fx + (size_t)film.nLayers * words, 1ull);
+            return;
+        }
+        unsigned long long *px = film.fx + (size_t)layer * words + ((size_t)iy * film.W + ix) * 3;
+        atomicAdd(px + 0, (unsigned long long)llrint((double)contrib.x * FILM_FX_SCALE));
+        atomicAdd(px + 1, (unsigned long long)llrint((double)contrib.y * FILM_FX_SCALE));
+        atomicAdd(px + 2, (unsigned long long)llrint((double)contrib.z * FILM_FX_SCALE));
+    }
+}
+// the label of pending entry k of the chain in slot i: read where a stored list is splatted again, written where a list is stored (an accepted large
+// step: every entry; an accepted small step: its one entry).  Nothing at all for the unlayered types.
+template <class FILM>
+LMC_D int PendingLabel(const FILM &film, const ChainArrays &A, int i, int k) {
+    if constexpr (FilmIsLayered<FILM>::value) return film.labels[(size_t)k * A.N + (A.chainId ? A.chainId[i] : i)];
+    else
+        return 0;
+}
+template <class FILM>
+LMC_D void StorePendingLabel(const FILM &film, const ChainArrays &A, int i, int k, int camDepth, int lightDepth) {
+    if constexpr (FilmIsLayered<FILM>::value) film.labels[(size_t)k * A.N + (A.chainId ? A.chainId[i] : i)] = (unsigned char)(camDepth * 16 + lightDepth);
+}
+
 // ---------------------------------------------------------------------------------------------- Gaussian
 struct Gauss {
     float mean[MAXPSS], covL[MAXPSS], invCov[MAXPSS];

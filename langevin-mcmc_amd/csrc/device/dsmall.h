@@ -789,11 +789,12 @@ LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays
             const float *p = A.curSplat + ((size_t)k * SPLAT_WORDS) * N + i;
             float s0 = p[0], s1 = p[N], s2 = p[2 * N], s3 = p[3 * N], s4 = p[4 * N];
             LMC_PIN5(s0, s1, s2, s3, s4);  // one round trip for the pending splat's five words
-            Splat(film, V2{s0, s1}, (1.0f - a) * V3{s2, s3, s4});
+            const int cl = PendingLabel(film, A, i, k);  // layered film only (dchain.h)
+            SplatT(film, V2{s0, s1}, (1.0f - a) * V3{s2, s3, s4}, cl >> 4, cl & 15);
         }
     }
     const V3 smallSplat = mala ? (pc.contrib * P.normalization) / pc.lsScore : pc.contrib * (P.normalization / pc.lsScore);
-    if (a > 0.0f && doSplat) Splat(film, pc.screenPos, a * smallSplat);
+    if (a > 0.0f && doSplat) SplatT(film, pc.screenPos, a * smallSplat, pc.camDepth, pc.lightDepth);
     st.wsum += curValid ? 1.0f : (a > 0.0f ? a : 0.0f);
 
     prof.Mark(PR_SPLAT);
@@ -808,6 +809,7 @@ LMC_D void SmallStepLean(const DScene &S, const DCache &cache, const ChainArrays
         float *p = A.curSplat + i;
         p[0] = pc.screenPos.x, p[N] = pc.screenPos.y, p[2 * N] = smallSplat.x, p[3 * N] = smallSplat.y, p[4 * N] = smallSplat.z;
         A.curSplatCount[i] = 1;
+        StorePendingLabel(film, A, i, 0, pc.camDepth, pc.lightDepth);
         if (mala) {  // mlt.cpp:133-142: chain.v1 / v2 = prop_new_v1 / v2 (whole vectors) -- unless they are known to be equal
             if (!(flags & F_VSYNC)) {
 #pragma unroll 4

@@ -400,7 +400,8 @@ LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A,
         const int n = A.curSplatCount[i];
         for (int k = 0; k < n; k++) {
             const float *p = A.curSplat + ((size_t)k * SPLAT_WORDS) * N + i;
-            Splat(film, V2{p[0], p[N]}, (1.0f - a) * V3{p[2 * N], p[3 * N], p[4 * N]});
+            const int cl = PendingLabel(film, A, i, k);  // layered film only (dchain.h)
+            SplatT(film, V2{p[0], p[N]}, (1.0f - a) * V3{p[2 * N], p[3 * N], p[4 * N]}, cl >> 4, cl & 15);
         }
     }
     // small-step splat value: mutation_small.h:48 `contrib * (normalization / lsScore)` vs mutation_mala.h:271
@@ -413,10 +414,10 @@ LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A,
             const float scale = P.normalization / propScoreSum;
             for (int k = 0; k < sink.count; k++) {
                 Contrib c = sink.Get(k);
-                Splat(film, c.screenPos, a * (c.contrib * scale));
+                SplatT(film, c.screenPos, a * (c.contrib * scale), c.camDepth, c.lightDepth);
             }
         } else {
-            Splat(film, pc.screenPos, a * smallSplat);
+            SplatT(film, pc.screenPos, a * smallSplat, pc.camDepth, pc.lightDepth);
         }
     }
     st.wsum += curValid ? 1.0f : (a > 0.0f ? a : 0.0f);
@@ -440,6 +441,7 @@ LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A,
                 float *p = A.curSplat + ((size_t)k * SPLAT_WORDS) * N + i;
                 V3 v = c.contrib * scale;
                 p[0] = c.screenPos.x, p[N] = c.screenPos.y, p[2 * N] = v.x, p[3 * N] = v.y, p[4 * N] = v.z;
+                StorePendingLabel(film, A, i, k, c.camDepth, c.lightDepth);
             }
             A.curSplatCount[i] = sink.count;
             // the old current state was valid iff the chain had run a MALA step since (chain.buffered)
@@ -462,6 +464,7 @@ LMC_D void StepChain(const DScene &S, const DCache &cache, const ChainArrays &A,
             float *p = A.curSplat + i;
             p[0] = pc.screenPos.x, p[N] = pc.screenPos.y, p[2 * N] = smallSplat.x, p[3 * N] = smallSplat.y, p[4 * N] = smallSplat.z;
             A.curSplatCount[i] = 1;
+            StorePendingLabel(film, A, i, 0, pc.camDepth, pc.lightDepth);
             if (lastMala) {  // mlt.cpp:133-142: chain.v1/v2 = prop_new_v1/v2 (whole vectors, whichever branch filled them last)
                 for (int k = 0; k < MAXPSS; k++) {
                     A.chV1[(size_t)k * N + i] = A.chPropNewV1[(size_t)k * N + i];

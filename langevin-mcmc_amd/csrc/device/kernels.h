@@ -69,15 +69,7 @@ void LaunchBidirMC(const lmcd::DScene &S, const lmcd::Film &film, int nThreads, 
 // layer McLayerOf gives its (camDepth, lightDepth)
 void LaunchMC(const lmcd::DScene &S, const lmcd::Film &film, int layerMode, int nLayers, bool bidirectional, int spp, int minDepth, int maxDepth, long long streamBegin,
               long long streamEnd, uint32_t *tabScratch, unsigned long long *counters, hipStream_t s);
-// The layer of technique (c, l) = (camDepth, lightDepth), path length L = c + l - 1 >= 1.  Mode 1 (by length): L - 1.  Mode 2 (by technique): the
-// lengths one after the other, length L with its L + 1 techniques l = 0 .. L: (L - 1)(L + 2) / 2 + l.  -1: no such technique.  With D = maxdepth a
-// film has McLayerCount layers, and a technique belongs to the table when its layer is below that.
-LMC_HD int McLayerOf(int mode, int c, int l) {
-    const int L = c + l - 1;
-    if (c < 1 || l < 0 || L < 1) return -1;
-    return mode == 1 ? L - 1 : (L - 1) * (L + 2) / 2 + l;
-}
-LMC_HD int McLayerCount(int mode, int maxDepth) { return mode == 1 ? maxDepth : mode == 2 ? maxDepth * (maxDepth + 3) / 2 : 0; }
+// (McLayerOf / McLayerCount, the numbering of the layers: dchain.h, beside the layered MLT film that shares it)
 void LaunchMCSumLayers(const long long *layers, long long *total, size_t n, int nLayers, hipStream_t s);  // total[i] = sum over k of layers[k * n + i]
 void LaunchMCSumLayers(const float *layers, float *total, size_t n, int nLayers, hipStream_t s);          // ... float adds in increasing k
 long long MCThreads(const lmcd::DScene &S, long long streamBegin, long long streamEnd);
@@ -100,6 +92,26 @@ void LaunchStepSmallLeanGrad(const lmcd::DScene &S, const lmcd::DCache *cache, c
 void LaunchStepSmallPlain(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::Film &film, const lmcd::StepParams &P,
                           const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads,
                           bool profile, hipStream_t s);  // one chain per thread: the grid is A.N slots; ldsStack = false: the private-stack instantiations whatever the tree
+// ... the same launches with the layered MLT film (dchain.h ChainFilmLayers, "film_layers"), each from a unit of its own (device/step_*_layers.hip)
+void LaunchStepLargeLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P,
+                     const int *list, const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s);
+void LaunchStepLargeMuxLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P,
+                     const int *list, const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s);
+void LaunchStepLargeCacheLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P,
+                     const int *list, const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s);
+void LaunchStepSmallGradLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P,
+                         const int *list, const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, hipStream_t s);
+void LaunchStepSmallLeanGradLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P, const int *list,
+                             const int *listCount, const lmcd::NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed,
+                             hipStream_t s);
+void LaunchStepSmallPlainLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P,
+                          const int *list, const int *listCount, const lmcd::NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads,
+                          bool profile, hipStream_t s);
+void LaunchMalaFinishLayers(const lmcd::DScene &S, const lmcd::DCache *cache, const lmcd::ChainArrays &A, const lmcd::ChainFilmLayers &film, const lmcd::StepParams &P, const lmcd::MalaPipe &M,
+                            const int *list, const int *listCount, int gridBlocks, hipStream_t s);
+// test probe of its splat routine (filmlayers.hip): n splats (screenXY, rgb, technique cl[2 i], cl[2 i + 1]) through SplatT into `film`; *outside += the finite
+// ones whose technique is outside the film's table
+void LaunchFilmLayerSplatProbe(const lmcd::ChainFilmLayers &film, int n, const float *screenXY, const float *rgb, const int *cl, unsigned long long *outside, hipStream_t s);
 // which instantiation of k_step_small that launch takes (step_small_plain.hip LeanFormOf)
 struct LeanForm {
     bool lds, glossy, prof, lightless, quant, tight;
@@ -195,5 +207,7 @@ void LaunchCkptUnpack(const lmcd::ChainArrays &A, int maxDepth, bool sampleCache
 void LaunchLatchKind(const lmcd::ChainArrays &A, const int *large, const int *generic, const int *lean, const int *counts, unsigned char *kindOf, hipStream_t s);
 // n rows of 48 words (include/lmc_abi.h LMC_ROW_WORDS), one wave per row; ids: rank-local chain ids in [0, A.N); which: 0 current, 1 init; kindOf may be nullptr
 void LaunchChainRows(const lmcd::ChainArrays &A, int which, const int *ids, int n, const unsigned char *kindOf, float *out, hipStream_t s);
+// the pending splat lists of n chains (lmc_chain_splats): counts[j] = list length, out[(j * cap + k) * 6 ..] = x, y, r, g, b, label (labels == nullptr: -1)
+void LaunchChainSplats(const lmcd::ChainArrays &A, const unsigned char *labels, const int *ids, int n, int cap, float *out, int *counts, hipStream_t s);
 // table[3][13][13][2] += the chain-steps of the step just run and those of them that were accepted, by (latched kind - 1, c, l of the state after it)
 void LaunchStepTable(const lmcd::ChainArrays &A, const unsigned char *kindOf, unsigned long long *table, hipStream_t s);

@@ -26,7 +26,14 @@ static void LaunchStepLargeT(const DScene &S, const DCache *cache, const ChainAr
     else
         LaunchKernArgs(k_step<FILM, true, false, false, false>, dim3(gridBlocks), dim3(256), 0, s, K);
 }
+#ifndef LMC_FILM_LAYERS_TU
 void LaunchStepLarge(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
                      const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {
     DispatchFilm(film, [&](const auto &f) { LaunchStepLargeT(S, cache, A, f, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, bvhStackNeed, blockThreads, s); });
 }
+#else  // the layered MLT film's unit includes this file and instantiates the launch with its own type
+void LaunchStepLargeLayers(const DScene &S, const DCache *cache, const ChainArrays &A, const ChainFilmLayers &film, const StepParams &P, const int *list, const int *listCount,
+                     const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {
+    LaunchStepLargeT(S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, bvhStackNeed, blockThreads, s);
+}
+#endif

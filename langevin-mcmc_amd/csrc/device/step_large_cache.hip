@@ -24,6 +24,12 @@ static void LaunchStepLargeCacheT(const DScene &S, const DCache *cache, const Ch
     else
         LaunchKernArgs(k_step<FILM, true, false, false, false, false, 2>, dim3(gridBlocks), dim3(256), 0, s, K);
 }
+#ifdef LMC_FILM_LAYERS_TU  // the layered MLT film's unit includes this file and instantiates the launch with its own type
+void LaunchStepLargeCacheLayers(const DScene &S, const DCache *cache, const ChainArrays &A, const ChainFilmLayers &film, const StepParams &P, const int *list, const int *listCount,
+                     const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {
+    LaunchStepLargeCacheT(S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, bvhStackNeed, blockThreads, s);
+}
+#else
 void LaunchStepLargeCache(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
                      const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int bvhStackNeed, int blockThreads, hipStream_t s) {
     DispatchFilm(film, [&](const auto &f) { LaunchStepLargeCacheT(S, cache, A, f, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, bvhStackNeed, blockThreads, s); });
@@ -43,3 +49,4 @@ __global__ void k_cache_probe(const DCache *cache, int dim, int n, const float *
 void LaunchCacheProbe(const DCache *cache, int dim, int n, const float *u, int *row, const float *query, const int *cl, float *pdf, hipStream_t s) {
     hipLaunchKernelGGL(k_cache_probe, dim3((n + 63) / 64), dim3(64), 0, s, cache, dim, n, u, row, query, cl, pdf);
 }
+#endif  // LMC_FILM_LAYERS_TU

@@ -29,6 +29,7 @@ __device__ __forceinline__ bool WantsGradient(const DCache &cache, const StepPar
 
 }  // namespace
 
+#ifndef LMC_FILM_LAYERS_TU  // step_mala_finish_layers.hip includes this file for k_mala_finish alone
 __global__ void __launch_bounds__(64) k_mala_begin(DScene S, const DCache *cachePtr, ChainArrays A, StepParams P, MalaPipe M, const int *list, const int *listCount) {
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
     LMC_RNG_JUMP_INIT();
@@ -150,6 +151,8 @@ __global__ void __launch_bounds__(64, LMC_MALA_MID_WAVES) k_mala_mid(DScene S, c
     BlockReduceStats(st, A.counters, A.weightSum, sStats);
 }
 
+#endif  // LMC_FILM_LAYERS_TU
+
 template <class FILM>
 __global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cachePtr, ChainArrays A, FILM film, StepParams P, MalaPipe M, const int *list, const int *listCount) {
     if ((int)(blockIdx.x * blockDim.x) >= *listCount) return;  // a block past the end of the work list: nothing to set up, nothing to do
@@ -195,12 +198,13 @@ __global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cach
             const int n = A.curSplatCount[i];
             for (int k = 0; k < n; k++) {
                 const float *p = A.curSplat + ((size_t)k * SPLAT_WORDS) * N + i;
-                Splat(film, V2{p[0], p[N]}, (1.0f - a) * V3{p[2 * N], p[3 * N], p[4 * N]});
+                const int cl = PendingLabel(film, A, i, k);  // layered film only (dchain.h)
+                SplatT(film, V2{p[0], p[N]}, (1.0f - a) * V3{p[2 * N], p[3 * N], p[4 * N]}, cl >> 4, cl & 15);
             }
         }
         // mutation_small.h:48 `contrib * (normalization / lsScore)` vs mutation_mala.h:271 `contrib * normalization / lsScore` (different rounding, kept)
         const V3 smallSplat = mala ? (pc.contrib * P.normalization) / pc.lsScore : pc.contrib * (P.normalization / pc.lsScore);
-        if (a > 0.0f) Splat(film, pc.screenPos, a * smallSplat);
+        if (a > 0.0f) SplatT(film, pc.screenPos, a * smallSplat, pc.camDepth, pc.lightDepth);
         st.wsum += curValid ? 1.0f : (a > 0.0f ? a : 0.0f);
         // ---- accept / reject, mlt.cpp:113-170
         const int sampleIdx = A.sampleIdx[i];
@@ -213,6 +217,7 @@ __global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cach
             float *p = A.curSplat + i;
             p[0] = pc.screenPos.x, p[N] = pc.screenPos.y, p[2 * N] = smallSplat.x, p[3 * N] = smallSplat.y, p[4 * N] = smallSplat.z;
             A.curSplatCount[i] = 1;
+            StorePendingLabel(film, A, i, 0, pc.camDepth, pc.lightDepth);
             if (mala) {  // mlt.cpp:133-142: chain.v1/v2 = prop_new_v1/v2 (whole vectors, whichever branch filled them last)
                 for (int k = 0; k < MAXPSS; k++) {
                     A.chV1[(size_t)k * N + i] = A.chPropNewV1[(size_t)k * N + i];
@@ -249,6 +254,7 @@ __global__ void __launch_bounds__(64) k_mala_finish(DScene S, const DCache *cach
     BlockReduceStats(st, A.counters, A.weightSum, sStats);
 }
 
+#ifndef LMC_FILM_LAYERS_TU
 void LaunchMalaBegin(const DScene &S, const DCache *cache, const ChainArrays &A, const StepParams &P, const MalaPipe &M, const int *list, const int *listCount, int gridBlocks,
                      hipStream_t s) {
     hipLaunchKernelGGL(k_mala_begin, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, P, M, list, listCount);
@@ -270,3 +276,9 @@ void LaunchMalaFinish(const DScene &S, const DCache *cache, const ChainArrays &A
                       int gridBlocks, hipStream_t s) {
     DispatchFilm(film, [&](const auto &f) { hipLaunchKernelGGL(k_mala_finish<std::decay_t<decltype(f)>>, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, f, P, M, list, listCount); });
 }
+#else
+void LaunchMalaFinishLayers(const DScene &S, const DCache *cache, const ChainArrays &A, const ChainFilmLayers &film, const StepParams &P, const MalaPipe &M, const int *list,
+                            const int *listCount, int gridBlocks, hipStream_t s) {
+    hipLaunchKernelGGL(k_mala_finish<ChainFilmLayers>, dim3(gridBlocks), dim3(64), 0, s, S, cache, A, film, P, M, list, listCount);
+}
+#endif

@@ -50,7 +50,14 @@ static void LaunchStepSmallLeanGradT(const DScene &S, const DCache *cache, const
     else
         hipLaunchKernelGGL((k_step_small_grad<FILM, false>), dim3(gridBlocks), dim3(blockThreads), ldsBytes, s, S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, stackWords);
 }
+#ifndef LMC_FILM_LAYERS_TU
 void LaunchStepSmallLeanGrad(const DScene &S, const DCache *cache, const ChainArrays &A, const Film &film, const StepParams &P, const int *list, const int *listCount,
                              const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed, hipStream_t s) {
     DispatchFilm(film, [&](const auto &f) { LaunchStepSmallLeanGradT(S, cache, A, f, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, blockThreads, bvhStackNeed, s); });
 }
+#else  // the layered MLT film's unit includes this file and instantiates the launch with its own type
+void LaunchStepSmallLeanGradLayers(const DScene &S, const DCache *cache, const ChainArrays &A, const ChainFilmLayers &film, const StepParams &P, const int *list, const int *listCount,
+                             const NextLists &next, float *gradBuf, int gradStride, bool glossy, int gridBlocks, int blockThreads, int bvhStackNeed, hipStream_t s) {
+    LaunchStepSmallLeanGradT(S, cache, A, film, P, list, listCount, next, gradBuf, gradStride, glossy, gridBlocks, blockThreads, bvhStackNeed, s);
+}
+#endif

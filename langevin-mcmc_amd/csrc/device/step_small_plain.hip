@@ -110,6 +110,7 @@ __global__ void __launch_bounds__(256, (GLOSSY && LIGHTLESS)               ? LMC
 //   lds: the traversal stack in LDS (ldsStack = false, LMC_LEAN_LDS=0 of host/context.cpp, is the private-stack fallback on a tree that would fit);
 //   prof: the region-timing instantiations (LDS stack only, exact nodes, with light sub-paths);  quant: the scene's choice of nodes (host/context.cpp
 //   UploadScene), LDS stack only;  tight: dscene.h Stk::kTight
+#ifndef LMC_FILM_LAYERS_TU  // (step_small_plain_layers.hip includes this file for the kernel and its launch function; it takes the same forms)
 LeanForm LeanFormOf(const DScene &S, int bvhDepth, bool glossy, bool ldsStack, bool profile) {
     LeanForm f{};
     f.lds = ldsStack && bvhDepth <= BVH_LDS_STACK;
@@ -120,6 +121,7 @@ LeanForm LeanFormOf(const DScene &S, int bvhDepth, bool glossy, bool ldsStack, b
     f.tight = !glossy && f.lightless && LMC_LEAN_TIGHT;
     return f;
 }
+#endif
 static std::atomic<bool> g_leanLogged{false};  // LMC_LEAN_LOG: one line per process
 
 template <class FILM>
@@ -175,6 +177,12 @@ static void LaunchStepSmallPlainT(const DScene &S, const DCache *cache, const Ch
         LMC_LAUNCH_SMALL(false, true);
 #undef LMC_LAUNCH_SMALL
 }
+#ifdef LMC_FILM_LAYERS_TU
+void LaunchStepSmallPlainLayers(const DScene &S, const DCache *cache, const ChainArrays &A, const ChainFilmLayers &film, const StepParams &P, const int *list, const int *listCount,
+                          const NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads, bool profile, hipStream_t s) {
+    LaunchStepSmallPlainT(S, cache, A, film, P, list, listCount, next, bvhDepth, glossy, ldsStack, blockThreads, profile, s);
+}
+#else
 void LeanLaunchPlan(int bvhStackNeed, int blockThreads, int *stackWords, int *ldsWordsPerThread, long long *ldsBytesPerBlock) {
     const int sw = LeanStackWords(bvhStackNeed);
     *stackWords = sw;
@@ -185,3 +193,4 @@ void LaunchStepSmallPlain(const DScene &S, const DCache *cache, const ChainArray
                           const NextLists &next, int bvhDepth, bool glossy, bool ldsStack, int blockThreads, bool profile, hipStream_t s) {
     DispatchFilm(film, [&](const auto &f) { LaunchStepSmallPlainT(S, cache, A, f, P, list, listCount, next, bvhDepth, glossy, ldsStack, blockThreads, profile, s); });
 }
+#endif  // LMC_FILM_LAYERS_TU

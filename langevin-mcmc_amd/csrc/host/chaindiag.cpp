@@ -145,6 +145,30 @@ int lmc_chain_rows(lmc_ctx *c, int which, const int *chain_ids, int n, float *ou
     LMC_CATCH(-1)
 }
 
+// the pending splat lists (A.curSplat) of chosen chains, gathered on the device: what row word 15 only counts
+int lmc_chain_splats(lmc_ctx *c, const int *chain_ids, int n, int cap, float *out, int *counts) {
+    LMC_TRY
+    if (c->N <= 0) throw std::runtime_error("lmc_chain_splats: the context holds no chains (lmc_chains_init or lmc_checkpoint_load first)");
+    static_assert(LMC_SPLAT_MAX_ENTRIES == MAXCONTRIB, "include/lmc_abi.h names the length a pending list can have");
+    if (cap < 1 || cap > MAXCONTRIB) throw std::runtime_error("lmc_chain_splats: cap is 1 .. " + std::to_string(MAXCONTRIB) + " entries per chain");
+    if (!out || !counts) throw std::runtime_error("lmc_chain_splats: out or counts is NULL");
+    const std::vector<int> local = LocalIds(c, chain_ids, n, "lmc_chain_splats");
+    HIP_CHECK(hipSetDevice(c->device));
+    DevBuf<int> ids, cnt;
+    DevBuf<float> rows;
+    AllocNamed(ids, (size_t)n, "lmc_chain_splats", "the chain ids");
+    AllocNamed(cnt, (size_t)n, "lmc_chain_splats", "the list lengths");
+    AllocNamed(rows, (size_t)n * cap * LMC_SPLAT_WORDS, "lmc_chain_splats", "the entries");
+    HIP_CHECK(hipMemcpyAsync(ids.p, local.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    LaunchChainSplats(c->A, c->filmLayers ? c->splatLabels.p : nullptr, ids.p, n, cap, rows.p, cnt.p, c->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, rows.p, (size_t)n * cap * LMC_SPLAT_WORDS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(counts, cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+    LMC_CATCH(-1)
+}
+
 int lmc_chain_trace_begin(lmc_ctx *c, const int *chain_ids, int n, int capacity_steps) {
     LMC_TRY
     if (c->N <= 0) throw std::runtime_error("lmc_chain_trace_begin: the context holds no chains (lmc_chains_init or lmc_checkpoint_load first)");

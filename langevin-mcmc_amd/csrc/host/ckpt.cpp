@@ -192,6 +192,7 @@ bool CkptLog() {
 void CkptSave(const std::vector<lmc_ctx *> &g, const char *path, const char *what) {
     if (!path || !*path) throw std::runtime_error(std::string(what) + ": no path");
     CkptCheckMembers(g, what, true);
+    for (lmc_ctx *c : g) RefuseLayered(c, what, "in this version a checkpoint holds an unlayered film only (nothing was written)");
     for (lmc_ctx *c : g)
         if (c->filmReduced) throw std::runtime_error(std::string(what) + ": the film already holds the sum over the ranks; a checkpoint of it would count the other ranks' share again");
     const auto t0 = std::chrono::steady_clock::now();
@@ -311,6 +312,7 @@ void CkptLoad(const std::vector<lmc_ctx *> &g, const char *path, const char *wha
     if (!path || !*path) throw std::runtime_error(std::string(what) + ": no path");
     if (g.empty()) throw std::runtime_error(std::string(what) + ": empty group");
     CkptCheckMembers(g, what, false);
+    for (lmc_ctx *c : g) RefuseLayered(c, what, "in this version a checkpoint holds an unlayered film only (the context is unchanged)");
     const auto t0 = std::chrono::steady_clock::now();
     CkptFile F;
     F.Open(path, "rb");

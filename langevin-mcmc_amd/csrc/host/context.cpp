@@ -415,6 +415,12 @@ int lmc_set_option(lmc_ctx *c, const char *name, double v) {
             throw std::runtime_error(std::string("film_exact: this context's chains are set up with the ") + (c->filmExact ? "fixed-point" : "float") + " film; the mode is chosen before lmc_chains_init / lmc_checkpoint_load");
         c->filmExact = v != 0;
         return 0;
+    } else if (n == "film_layers") {  // the MLT film split by path length (1) or technique (2), host/filmlayers.cpp: chosen before lmc_chains_init, like film_exact
+        if (v != 0 && v != 1 && v != 2) throw std::runtime_error("film_layers: 0 (off), 1 (by path length) or 2 (by technique) expected");
+        if ((int)v != c->filmLayers && c->N > 0)
+            throw std::runtime_error("film_layers: this context's chains are set up with film_layers = " + std::to_string(c->filmLayers) + "; the mode is chosen before lmc_chains_init");
+        c->filmLayers = (int)v;
+        return 0;
     } else if (n == "step_table") {  // the per-technique step table (chaindiag.cpp): counts from the next step on
         DiagSetStepTable(c, v != 0);
         return 0;
@@ -455,6 +461,7 @@ int lmc_get_option(lmc_ctx *c, const char *name, double *v) {
     else if (n == "bvh_quantised") *v = c->S.qnodes ? 1 : 0;            // back-end state, not a <dpt> option: the node format of the scene's hot launches ...
     else if (n == "bvh_thick_flat_share") *v = c->thickFlatShare;       // ... and the figure it was chosen by (UploadScene)
     else if (n == "film_exact") *v = c->filmExact ? 1 : 0;
+    else if (n == "film_layers") *v = c->filmLayers;
     else if (n == "mc_film_exact") *v = c->mcExactOpt ? 1 : 0;
     else if (n == "mc_layers") *v = c->mcLayersOpt;
     else if (n == "mc_launch_streams") *v = (double)c->mcLaunchStreams;
@@ -1079,6 +1086,7 @@ void lmc_host::SetUpChains(lmc_ctx *c, const ChainSetUp &U) {
     if (c->filmExact) c->filmFx.Alloc(c->film.n + 1);  // zeroed; the last word is the film_overflow counter
     else
         c->filmFx.Free();
+    LayersAlloc(c);  // "film_layers": the layers and the labels of the pending lists
     HIP_CHECK(hipStreamSynchronize(s));
     WarmStepLaunches(c);
     c->chainsSince = std::chrono::steady_clock::now();
@@ -1089,6 +1097,7 @@ namespace {
 void RunInit(const std::vector<lmc_ctx *> &g, long long numInitSamples, int numChainsTotal, int initThreads, const std::vector<std::pair<int, int>> &ranges,
              long long perChain, long long chainsNeedExtra) {
     if (numInitSamples <= 0) throw std::runtime_error("lmc_chains_init: no init samples");
+    for (lmc_ctx *c : g) LayersCheckInit(c, g.size() > 1 ? "lmc_group_chains_init" : "lmc_chains_init");  // before anything changes
     std::vector<std::unique_ptr<InitJob>> jobs;
     for (size_t k = 0; k < g.size(); k++) {
         lmc_ctx *c = g[k];
@@ -1123,6 +1132,9 @@ void RunInit(const std::vector<lmc_ctx *> &g, long long numInitSamples, int numC
 // What the film merge of an in-process group needs, set up ONCE when the group is: direct peer access between the members' devices (checked
 // with hipDeviceCanAccessPeer, enabled once per ordered pair; without it the runtime stages every peer copy through the host), every member's
 // staging for the slices it pulls, the events the merge is ordered by.  Nothing is allocated inside lmc_group_film_reduce.
+// the words lmc_group_film_reduce sums: the film, or with "film_layers" every layer and the overflow word behind them
+static size_t MergeWords(const lmc_ctx *c) { return c->filmLayers ? (size_t)c->filmNLayers * c->film.n + 1 : c->film.n; }
+static long long *MergeFx(lmc_ctx *c) { return c->filmLayers ? c->filmLayersFx.p : c->filmFx.p; }
 void lmc_host::GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
     const size_t n = g.size();
     std::vector<int> devs;
@@ -1145,7 +1157,7 @@ void lmc_host::GroupSetUpMerge(const std::vector<lmc_ctx *> &g) {
         HIP_CHECK(hipSetDevice(c->device));
         c->groupDevices = (int)devs.size(), c->groupPeerPairs = pairs, c->groupPeerEnabled = enabled;
         if (n > 1) {
-            const size_t slice = (c->film.n + n - 1) / n;
+            const size_t slice = (MergeWords(c) + n - 1) / n;
             if (c->filmExact) c->filmStageFx.Alloc(slice * (n - 1), false), c->filmStage.Free();
             else
                 c->filmStage.Alloc(slice * (n - 1), false), c->filmStageFx.Free();
@@ -1179,6 +1191,10 @@ int lmc_group_chains_init(lmc_ctx **ctxs, int n, long long numInitSamples, int n
     for (int r = 1; r < n; r++)  // before anything changes: the refused contexts stay as they were
         if (g[r]->filmExact != g[0]->filmExact)
             throw std::runtime_error("lmc_group_chains_init: the members differ in film_exact (member 0: " + std::to_string((int)g[0]->filmExact) + ", member " + std::to_string(r) + ": " + std::to_string((int)g[r]->filmExact) + "); a group's films are merged in one format");
+    for (int r = 1; r < n; r++)
+        if (g[r]->filmLayers != g[0]->filmLayers)
+            throw std::runtime_error("lmc_group_chains_init: the members differ in film_layers (member 0: " + std::to_string(g[0]->filmLayers) + ", member " + std::to_string(r) + ": " + std::to_string(g[r]->filmLayers) + "); a group's films are merged layer by layer");
+    for (int r = 0; r < n; r++) LayersCheckInit(g[r], "lmc_group_chains_init");
     for (int r = 0; r < n; r++) {
         for (lmc_ctx *peer : g[r]->group)  // leaving an earlier group: its other members must not keep a pointer to this context as a peer
             if (peer != g[r]) peer->group.clear(), peer->world = 1, peer->rank = 0;
@@ -1463,8 +1479,13 @@ StepParams lmc_host::MakeStepParams(const lmc_ctx *c) {
 namespace {
 // which large-step / generic small-step kernel the options in force select (cnt: the three list lengths on the device)
 Film StepFilm(lmc_ctx *c) { return c->filmExact ? FilmFx(c->filmFx.p, c->S.cam.width, c->S.cam.height) : Film{c->film.p, c->S.cam.width, c->S.cam.height}; }
+// "film_layers": every launch below takes its layered form (device/step_*_layers.hip) with the film LayeredFilm(c) instead; `film` is then not used
 void LaunchLarge(lmc_ctx *c, const Film &film, const StepParams &P, int cur, const int *cnt, const NextLists &next, hipStream_t sL) {
     const bool mux = c->scene->options.largeStepMultiplexed;
+    if (c->filmLayers) {
+        (c->S.opt.sampleCache ? LaunchStepLargeCacheLayers : mux ? LaunchStepLargeMuxLayers : LaunchStepLargeLayers)(c->S, c->cacheDev.p, c->A, LayeredFilm(c), P, c->lists[cur][0].p, cnt + 0, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, c->largeLdsStack ? c->bvhDepth : 1 << 30, c->largeBlock, sL);
+        return;
+    }
     (c->S.opt.sampleCache ? LaunchStepLargeCache : mux ? LaunchStepLargeMux : LaunchStepLarge)(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][0].p, cnt + 0, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, c->largeLdsStack ? c->bvhDepth : 1 << 30, c->largeBlock, sL);
 }
 void LaunchGeneric(lmc_ctx *c, const Film &film, const StepParams &P, int cur, const int *cnt, const NextLists &next, hipStream_t sG) {
@@ -1541,11 +1562,23 @@ void LaunchGeneric(lmc_ctx *c, const Film &film, const StepParams &P, int cur, c
         LaunchMalaMid(c->S, c->cacheDev.p, c->A, P, M, list, n, c->bvhDepth, c->S.glossy != 0, laneGrid, sG);
         LaunchBinsCompact(M.bins[1], list, n, laneGrid, sG);
         LaunchMalaGrad(M.rec, M.bins[1], N, c->S.sceneParams, M.gout, c->h2HessGrid, sG);
-        LaunchMalaFinish(c->S, c->cacheDev.p, c->A, film, P, M, list, n, laneGrid, sG);
-    } else if (c->needGeneric && c->leanGrad && !c->anyDeepCache && !c->S.opt.useLightCoord && !c->S.opt.sampleCache && c->bvhDepth <= BVH_LDS_STACK)
-        LaunchStepSmallLeanGrad(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->genericTokenOnly ? 64 : c->stepGrid * 4, 64, c->bvhDepth, sG);
-    else if (c->needGeneric)
-        LaunchStepSmallGrad(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, sG);
+        if (c->filmLayers) LaunchMalaFinishLayers(c->S, c->cacheDev.p, c->A, LayeredFilm(c), P, M, list, n, laneGrid, sG);
+        else
+            LaunchMalaFinish(c->S, c->cacheDev.p, c->A, film, P, M, list, n, laneGrid, sG);
+    } else if (c->needGeneric && c->leanGrad && !c->anyDeepCache && !c->S.opt.useLightCoord && !c->S.opt.sampleCache && c->bvhDepth <= BVH_LDS_STACK) {
+        if (c->filmLayers) LaunchStepSmallLeanGradLayers(c->S, c->cacheDev.p, c->A, LayeredFilm(c), P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->genericTokenOnly ? 64 : c->stepGrid * 4, 64, c->bvhDepth, sG);
+        else
+            LaunchStepSmallLeanGrad(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->genericTokenOnly ? 64 : c->stepGrid * 4, 64, c->bvhDepth, sG);
+    } else if (c->needGeneric) {
+        if (c->filmLayers) LaunchStepSmallGradLayers(c->S, c->cacheDev.p, c->A, LayeredFilm(c), P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, sG);
+        else
+            LaunchStepSmallGrad(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][1].p, cnt + 1, next, c->gradBuf.p, c->gradStride, c->S.glossy != 0, c->stepGrid, sG);
+    }
+}
+void LaunchLean(lmc_ctx *c, const Film &film, const StepParams &P, const int *list, const int *cnt, const NextLists &next, hipStream_t s) {
+    if (c->filmLayers) LaunchStepSmallPlainLayers(c->S, c->cacheDev.p, c->A, LayeredFilm(c), P, list, cnt, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
+    else
+        LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, list, cnt, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
 }
 // first half of one step: the three step launches; then, while a cache is filling, this rank's pushes into its stage.
 // Returns whether the ranks have pushes to exchange.
@@ -1635,7 +1668,7 @@ bool StepPhase1(lmc_ctx *c, lmc_ctx::StepEvents &ev) {
     if (c->timing) HIP_CHECK(hipEventRecord(ev.e[1], s));
     // every small step of an H2MC render runs the pipeline: the lean list is empty by construction (QueueNext, LeanDims), and its launch of
     // four-wave blocks sat in the queue for the length of the large-step launch
-    if (!c->S.opt.h2mc) LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[cur][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
+    if (!c->S.opt.h2mc) LaunchLean(c, film, P, c->lists[cur][2].p, cnt + 2, next, s);
     if (c->timing) HIP_CHECK(hipEventRecord(ev.e[2], s));
     if (c->overlap) {
         HIP_CHECK(hipEventRecord(c->joinEvent[0], sL));
@@ -1741,6 +1774,10 @@ static void WarmStepLaunches(lmc_ctx *c) {
     const Film film = StepFilm(c);
     const StepParams P = MakeStepParams(c);
     c->warmCounts.Alloc(4);  // zero-filled: three empty lists
+    // DevBuf::Alloc zeroes with hipMemset on the null stream, which returns before the words are written, and the side streams are created
+    // hipStreamNonBlocking: they do not wait for the null stream.  A warm launch that read a count before its zero had landed would step whatever the
+    // (uninitialised) generic list names.  Seen once as an illegal access in this function, in a layered context, whose film's zeroing is queued in front.
+    HIP_CHECK(hipStreamSynchronize(nullptr));
     NextLists next{c->lists[1][0].p, c->lists[1][1].p, c->lists[1][2].p, c->listCounts[1].p};
     hipStream_t s = c->stream, sL = c->overlap ? c->sideStream[0] : s, sG = c->overlap ? c->sideStream[1] : s;
     const int *cnt = c->warmCounts.p;
@@ -1751,7 +1788,7 @@ static void WarmStepLaunches(lmc_ctx *c) {
         LaunchGeneric(c, film, P, 0, cnt, next, sG);
         c->allCachesReady = false;
     }
-    LaunchStepSmallPlain(c->S, c->cacheDev.p, c->A, film, P, c->lists[0][2].p, cnt + 2, next, c->bvhDepth, c->S.glossy != 0, c->leanLdsStack, c->leanBlock, c->profileLean, s);
+    LaunchLean(c, film, P, c->lists[0][2].p, cnt + 2, next, s);
     HIP_CHECK(hipStreamSynchronize(sL));
     HIP_CHECK(hipStreamSynchronize(sG));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -1779,6 +1816,7 @@ namespace {
 // last cache became ready); plain MLT never fills a cache, so its chains run resident from the first step.
 bool ResidentEligible(lmc_ctx *c) {
     if (c->residentSteps <= 0 || c->S.opt.h2mc) return false;
+    if (c->filmLayers) return false;  // the resident launch is not layered: lock step, by that schedule's contract the same trajectories
     if (c->diag && DiagNeedsLockStep(c)) return false;  // a resident launch cannot be observed between its mutations
     for (const lmc_ctx *m : c->group)                    // ... and the members of a group take the same schedule (RunSteps: they meet at barriers in lock step)
         if (m->diag && DiagNeedsLockStep(m)) return false;
@@ -2005,6 +2043,7 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
         if (c->filmReduced) throw std::runtime_error("lmc_group_film_reduce: the films already hold the sum over the members; step or clear them first");
         if (c->film.n != g[0]->film.n) throw std::runtime_error("lmc_group_film_reduce: the members' films differ in size");
         if (c->filmExact != g[0]->filmExact) throw std::runtime_error("lmc_group_film_reduce: the members differ in film_exact");
+        if (c->filmLayers != g[0]->filmLayers) throw std::runtime_error("lmc_group_film_reduce: the members differ in film_layers");
     }
     const bool exact = g[0]->filmExact;  // int64 slices, integer adds: the sum is the same in any order
     if (out_ms)  // only so that the reported time is the merge's own: the merge is stream-ordered behind the members' steps either way
@@ -2013,7 +2052,7 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
             HIP_CHECK(hipStreamSynchronize(c->stream));
         }
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t total = g[0]->film.n, slice = (total + n - 1) / n;
+    const size_t total = MergeWords(g[0]), slice = (total + n - 1) / n;  // "film_layers": layer by layer, the layers being one array
     auto sliceLen = [&](int k) { return (size_t)k * slice >= total ? (size_t)0 : std::min(slice, total - (size_t)k * slice); };
     if (n > 1) {
         for (lmc_ctx *c : g) {  // every member's film (and weight sum) is final once its stream gets here
@@ -2030,8 +2069,8 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
                 if (m == k || sliceLen(k) == 0) continue;
                 if (exact) {
                     long long *st = c->filmStageFx.p + (size_t)slot * slice;
-                    HIP_CHECK(hipMemcpyPeerAsync(st, c->device, g[m]->filmFx.p + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(long long), c->stream));
-                    LaunchAddIntoI64(c->filmFx.p + (size_t)k * slice, st, sliceLen(k), c->stream);
+                    HIP_CHECK(hipMemcpyPeerAsync(st, c->device, MergeFx(g[m]) + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(long long), c->stream));
+                    LaunchAddIntoI64(MergeFx(c) + (size_t)k * slice, st, sliceLen(k), c->stream);
                 } else {
                     float *st = c->filmStage.p + (size_t)slot * slice;
                     HIP_CHECK(hipMemcpyPeerAsync(st, c->device, g[m]->film.p + (size_t)k * slice, g[m]->device, sliceLen(k) * sizeof(float), c->stream));
@@ -2048,7 +2087,7 @@ int lmc_group_film_reduce(lmc_ctx **ctxs, int n, double *out_ms) {
             for (int m = 0; m < n; m++) {
                 if (m == k) continue;
                 HIP_CHECK(hipStreamWaitEvent(c->stream, g[m]->sliceReducedEvent, 0));  // == weightsCopiedEvent of m: m has read this member's scalar
-                if (sliceLen(m) && exact) HIP_CHECK(hipMemcpyPeerAsync(c->filmFx.p + (size_t)m * slice, c->device, g[m]->filmFx.p + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(long long), c->stream));
+                if (sliceLen(m) && exact) HIP_CHECK(hipMemcpyPeerAsync(MergeFx(c) + (size_t)m * slice, c->device, MergeFx(g[m]) + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(long long), c->stream));
                 else if (sliceLen(m)) HIP_CHECK(hipMemcpyPeerAsync(c->film.p + (size_t)m * slice, c->device, g[m]->film.p + (size_t)m * slice, g[m]->device, sliceLen(m) * sizeof(float), c->stream));
             }
             LaunchSumF64(c->weightSum.p, c->weightStage.p, n, c->stream);
@@ -2077,6 +2116,7 @@ int lmc_host_issue_timing(lmc_ctx *c, double *ms, long long *steps) {
 int lmc_film_read(lmc_ctx *c, float *rgb) {
     LMC_TRY
     HIP_CHECK(hipSetDevice(c->device));
+    SyncLayerSum(c);  // "film_layers": filmFx = the sum of the layers
     if (c->filmFx.p) LaunchFilmFixedToFloat(c->filmFx.p, c->film.p, c->film.n, c->stream);  // exact mode: converted on the device, float(double(q) * 2^-32)
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(rgb, c->film.p, c->film.n * sizeof(float), hipMemcpyDeviceToHost));
@@ -2088,6 +2128,7 @@ int lmc_film_read_fixed(lmc_ctx *c, long long *out) {
     LMC_TRY
     if (!c->filmFx.p) throw std::runtime_error("lmc_film_read_fixed: this context's film is the float film (set film_exact before lmc_chains_init)");
     HIP_CHECK(hipSetDevice(c->device));
+    SyncLayerSum(c);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(out, c->filmFx.p, c->film.n * sizeof(long long), hipMemcpyDeviceToHost));
     return 0;
@@ -2099,6 +2140,7 @@ int lmc_film_overflow(lmc_ctx *c, long long *n) {
     *n = 0;
     if (!c->filmFx.p) return 0;  // the float film drops nothing
     HIP_CHECK(hipSetDevice(c->device));
+    SyncLayerSum(c);
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipMemcpy(n, c->filmFx.p + c->film.n, sizeof(long long), hipMemcpyDeviceToHost));
     return 0;
@@ -2175,11 +2217,13 @@ int lmc_film_allreduce(lmc_ctx *c) {
     LMC_TRY
     HIP_CHECK(hipSetDevice(c->device));
     if (!c->comm) throw std::runtime_error("lmc_film_allreduce before lmc_comm_init");
+    if (c->world > 1) RefuseLayered(c, "lmc_film_allreduce", "in this version a layered film is merged inside one process only (lmc_group_film_reduce); nothing was reduced");
     if (c->filmReduced) throw std::runtime_error("lmc_film_allreduce: the film already holds the sum over ranks (a second in-place sum would count every rank's splats again); step or clear the film first");
     c->filmReduced = true;
     // in place on the device film, on the stream the step kernels run on: ordered after the last splat, no host staging
     // (exact mode: the int64 words and, behind them, the overflow counter -- integer sums, the same on every rank whatever the order)
-    if (c->filmFx.p) RcclCheck(GetRccl().AllReduce(c->filmFx.p, c->filmFx.p, c->filmFx.n, ncclInt64, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film, int64)");
+    if (c->filmLayers) RcclCheck(GetRccl().AllReduce(c->filmLayersFx.p, c->filmLayersFx.p, c->filmLayersFx.n, ncclInt64, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film layers, int64)");  // one rank: the identity
+    else if (c->filmFx.p) RcclCheck(GetRccl().AllReduce(c->filmFx.p, c->filmFx.p, c->filmFx.n, ncclInt64, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film, int64)");
     else
         RcclCheck(GetRccl().AllReduce(c->film.p, c->film.p, c->film.n, ncclFloat32, ncclSum, (ncclComm_t)c->comm, c->stream), "ncclAllReduce(film)");
     // the scalars that normalise the merged image: sum of splat weights (double) -- `normalization` itself is identical on
@@ -2190,15 +2234,24 @@ int lmc_film_allreduce(lmc_ctx *c) {
 }
 
 void *lmc_film_device_ptr(lmc_ctx *c, long long *nFloats) {
+    LMC_TRY
     if (nFloats) *nFloats = (long long)c->film.n;
+    if (c->filmLayers && c->filmLayersFx.p) {  // "film_layers": the sum of the layers as it stands now; a failed sum returns NULL with lmc_last_error set
+        HIP_CHECK(hipSetDevice(c->device));
+        SyncLayerSum(c);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
     if (c->filmFx.p) return c->filmFx.p;  // exact mode: int64 words, the same count
     return c->film.p;
+    LMC_CATCH(nullptr)
 }
 
 int lmc_film_clear(lmc_ctx *c) {
     LMC_TRY
     HIP_CHECK(hipMemsetAsync(c->film.p, 0, c->film.n * sizeof(float), c->stream));
     if (c->filmFx.p) HIP_CHECK(hipMemsetAsync(c->filmFx.p, 0, c->filmFx.n * sizeof(long long), c->stream));  // the words and the overflow counter
+    if (c->filmLayersFx.p) HIP_CHECK(hipMemsetAsync(c->filmLayersFx.p, 0, c->filmLayersFx.n * sizeof(long long), c->stream));  // "film_layers": every layer
     c->filmReduced = false;
     return 0;
     LMC_CATCH(-1)

@@ -102,7 +102,15 @@ struct lmc_ctx {
     // the film_overflow counter; `film` then only receives the converted floats of lmc_film_read.  directFilm and mcFilm stay float in either mode.
     DevBuf<long long> filmFx;
     bool filmExact = false;
-    DevBuf<float> mcFilm;                   // lmc_mc_render's film (the mc integrator), weighted by 1 / spp
+    // the layered MLT film ("film_layers", INTEGRATION.md "Layered MLT film"; exact mode only): the MLT splats go to filmLayersFx, filmNLayers exact films of
+    // W*H*3 words one after the other and ONE overflow word behind them, split by path length (1) or technique (2).  filmFx then only receives their sum
+    // (SyncLayerSum, in front of every read of it), as `film` receives the converted floats.  splatLabels: the techniques of the pending splat lists, one
+    // byte per entry by CHAIN id (dchain.h ChainFilmLayers).  Both allocated by SetUpChains in this mode only.
+    int filmLayers = 0;  // the option; fixed once chains are set up, like filmExact
+    int filmNLayers = 0;
+    DevBuf<long long> filmLayersFx;
+    DevBuf<unsigned char> splatLabels;
+    DevBuf<float> mcFilm;                  // lmc_mc_render's film (the mc integrator), weighted by 1 / spp
     DevBuf<unsigned long long> mcCounters;  // [paths traced, contributions splatted] of the last lmc_mc_render (exact mode: since the film was last cleared)
     // exact mode of the mc film ("mc_film_exact", INTEGRATION.md "Exact mc film"): the contributions go unweighted to mcFilmFx, W*H*3 fixed-point words followed
     // by the overflow counter; mcFilm then only receives lmc_mc_read's converted floats, divided by mcDivisor (the spp of the last render / accumulate call)
@@ -325,6 +333,12 @@ void DiagChainsReset(lmc_ctx *c);           // SetUpChains (lmc_chains_init, lmc
 void DiagSetStepTable(lmc_ctx *c, bool on);  // lmc_set_option "step_table"
 bool DiagStepTableOn(const lmc_ctx *c);
 void DiagFree(lmc_ctx *c);
+// filmlayers.cpp (the layered MLT film, "film_layers"), for context.cpp and ckpt.cpp
+ChainFilmLayers LayeredFilm(const lmc_ctx *c);                // the film the layered step launches splat into
+void LayersCheckInit(const lmc_ctx *c, const char *what);     // lmc_chains_init / lmc_group_chains_init: the mode needs film_exact and refuses H2MC; throws before anything changes
+void LayersAlloc(lmc_ctx *c);                                  // SetUpChains: the layers (zeroed) and the label array, or nothing with the mode off
+void SyncLayerSum(lmc_ctx *c);                                 // filmFx = the sum of the layers, overflow word included (stream-ordered; nothing with the mode off)
+void RefuseLayered(const lmc_ctx *c, const char *what, const char *why);  // throws "<what>: ... film_layers ..." while the mode is on
 // ckpt.cpp, for mcrender.cpp (a state file of the mc film carries the same fingerprint)
 uint64_t HashSceneFiles(const lmc::Scene &sc);
 

@@ -61,9 +61,12 @@ def main():
     a, b = {key(n): v for n, v in a.items()}, {key(n): v for n, v in b.items()}
     names = {n: n for n in set(a) | set(b)}
 
+    def short(d):  # without the parameter list; "(anonymous namespace)::" stays, it is part of the name
+        return re.sub(r"\((?!anonymous namespace\)).*", "", d)
+
     def base(n):
         d = names[n]
-        d = re.sub(r"^void ", "", d)
+        d = re.sub(r"^void ", "", d).replace("(anonymous namespace)::", "")
         return re.split(r"[<(]", d, 1)[0].split("::")[-1]
 
     worse = []
@@ -71,7 +74,7 @@ def main():
     for n in sorted(names, key=lambda k: names[k]):
         if only and base(n) not in only:
             continue
-        print("\n" + re.sub(r"\(.*", "", names[n]))
+        print("\n" + short(names[n]))
         if n not in a or n not in b:
             one = a[n] if n in a else b[n]
             print("    only in the %s log: %s" % ("first" if n in a else "second", ", ".join("%s %s" % (f, one[f]) for f in SHOWN)))
@@ -83,7 +86,7 @@ def main():
             worse.append(names[n])
     print("\nkernels with more VGPRs, more scratch or fewer waves per SIMD in the second log: %d" % len(worse))
     for w in worse:
-        print("    " + re.sub(r"\(.*", "", w))
+        print("    " + short(w))
     return 1 if worse else 0
 
 

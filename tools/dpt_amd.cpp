@@ -30,6 +30,10 @@
 // --mc-layers length|technique (mc scenes only; lmc_set_option "mc_layers", INTEGRATION.md "Layered mc film"): the render split by path length or by technique.
 // The usual EXR holds the sum of the layers; beside it every non-empty layer is written under the same name with _L<length> (two digits) or
 // _c<camDepth>_l<lightDepth> before .exr.  One device, no --checkpoint / --resume in this version.
+// --film-layers length|technique (mcmc scenes; lmc_set_option "film_layers", INTEGRATION.md "Layered MLT film"): the MLT film split the same way.  It implies
+// --exact-film; the usual EXR is, byte for byte, the one an --exact-film run without the flag writes, and every non-empty layer is written beside it with
+// the suffixes above, scaled as the indirect film is before the direct film is added (1 / spp).  Works with --gpus / --devices; with --checkpoint /
+// --resume it is an error at start.
 // Chain diagnostics (mcmc scenes on one device; include/lmc_abi.h "Chain diagnostics"): --trace-chains a,b,.. --trace-file F [--trace-steps S, default 1024]
 // records the rows of the listed chains over the first S steps of this invocation and writes F (little-endian: "LMCTRACE", u32 version 1, u32 row words,
 // u32 n, u32 steps, i64 first step, n x i32 chain ids, then steps x n x row-words floats); --step-table prints the non-empty cells of lmc_step_table,
@@ -260,6 +264,7 @@ static void PrintHelp() {
            "  --exact-film                64-bit fixed-point film, bit-equal from run to run\n"
            "  --spp N, --max-spp K        integrator=mc: samples per pixel / render the sample indices below K only\n"
            "  --mc-layers length|technique   integrator=mc: the film split by path length or by technique\n"
+           "  --film-layers length|technique integrator=mcmc: the MLT film split the same way (implies --exact-film; no --checkpoint / --resume)\n"
            "  --trace-chains a,b,..       integrator=mcmc, one device: record the rows of these chains after every step ...\n"
            "  --trace-file FILE           ... and write them to FILE (\"LMCTRACE\", version 1; langevin-mcmc_amd trace_file_read)\n"
            "  --trace-steps S             ... over the first S steps of this invocation (default 1024)\n"
@@ -281,6 +286,7 @@ int main(int argc, char *argv[]) {
     bool exactFilm = false;
     int mcSpp = 0, mcMaxSpp = 0;  // --spp / --max-spp (integrator = mc)
     int mcLayers = 0;              // --mc-layers length|technique (integrator = mc)
+    int filmLayers = 0;            // --film-layers length|technique (integrator = mcmc)
     std::vector<int> traceChains;  // --trace-chains / --trace-file / --trace-steps, --step-table (integrator = mcmc, one device)
     std::string traceFile;
     int traceSteps = 1024;
@@ -319,7 +325,14 @@ int main(int argc, char *argv[]) {
         else if (a == "--exact-film") exactFilm = true;
         else if (a == "--spp") mcSpp = std::stoi(argv[++i]);
         else if (a == "--max-spp") mcMaxSpp = std::stoi(argv[++i]);
-        else if (a == "--mc-layers") {
+        else if (a == "--film-layers") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            filmLayers = m == "length" ? 1 : m == "technique" ? 2 : 0;
+            if (filmLayers == 0) {
+                fprintf(stderr, "--film-layers: length or technique expected\n");
+                return 2;
+            }
+        } else if (a == "--mc-layers") {
             const std::string m = i + 1 < argc ? argv[++i] : "";
             mcLayers = m == "length" ? 1 : m == "technique" ? 2 : 0;
             if (mcLayers == 0) {
@@ -375,6 +388,10 @@ int main(int argc, char *argv[]) {
                 fprintf(stderr, "%s: %s has integrator=mc; only the Markov chains of an integrator=mcmc scene can be traced\n", wantTrace ? "--trace-chains" : "--step-table", filename.c_str());
                 return 2;
             }
+            if (filmLayers != 0) {
+                fprintf(stderr, "--film-layers: %s has integrator=mc; its film is layered with --mc-layers\n", filename.c_str());
+                return 2;
+            }
             if (mltFlags) printf("--chains / --resident / --init-threads: ignored by integrator=mc\n");
             McFlags mf;
             mf.layers = mcLayers;
@@ -384,6 +401,18 @@ int main(int argc, char *argv[]) {
             if (rc != 0) return rc;
             printf("Done!\n");
             continue;
+        }
+        if (filmLayers != 0) {
+            if (!checkpointPath.empty() || !resumePath.empty()) {
+                fprintf(stderr, "--film-layers: a layered MLT film has no checkpoint in this version (no --checkpoint / --resume)\n");
+                return 2;
+            }
+            exactFilm = true;
+            for (lmc_ctx *c : ctxs)
+                if (lmc_set_option(c, "film_layers", filmLayers) != 0) {
+                    fprintf(stderr, "%s\n", lmc_last_error());
+                    return 1;
+                }
         }
         if (mcLayers != 0) {
             fprintf(stderr, "--mc-layers: %s has integrator=mcmc; only the film of an integrator=mc scene can be layered\n", filename.c_str());
@@ -521,6 +550,34 @@ int main(int argc, char *argv[]) {
         if (lmc_image_write_exr(out.c_str(), img.data(), W, H) != 0) {
             fprintf(stderr, "%s\n", lmc_last_error());
             return 1;
+        }
+        if (filmLayers != 0) {  // every non-empty layer beside the image, scaled as the indirect film above (after a merge every member holds the sums: member 0's)
+            int mode = 0, nLayers = 0, written = 0;
+            std::vector<int> cl(2 * 128);
+            if (lmc_film_layer_info(ctx, &mode, &nLayers, cl.data(), 128) != 0 || nLayers > 128) {
+                fprintf(stderr, "%s\n", nLayers > 128 ? "--film-layers: more than 128 layers" : lmc_last_error());
+                return 1;
+            }
+            std::vector<float> layer((size_t)W * H * 3);
+            for (int k = 0; k < nLayers; k++) {
+                if (lmc_film_read_layer(ctx, k, layer.data()) != 0) {
+                    fprintf(stderr, "%s\n", lmc_last_error());
+                    return 1;
+                }
+                if (std::all_of(layer.begin(), layer.end(), [](float v) { return v == 0.0f; })) continue;
+                for (float &v : layer) v = iw * v;
+                char tag[64];
+                if (mode == 1) snprintf(tag, sizeof(tag), "_L%02d", cl[2 * k]);
+                else
+                    snprintf(tag, sizeof(tag), "_c%d_l%d", cl[2 * k], cl[2 * k + 1]);
+                const std::string name = out.substr(0, out.size() - 4) + tag + ".exr";
+                if (lmc_image_write_exr(name.c_str(), layer.data(), W, H) != 0) {
+                    fprintf(stderr, "%s\n", lmc_last_error());
+                    return 1;
+                }
+                written++;
+            }
+            printf("Layered film (%s): %d of %d layers are non-empty and written beside the image\n", mode == 1 ? "by path length" : "by technique", written, nLayers);
         }
         long long mutations = 0, dropped = 0;
         for (lmc_ctx *c : ctxs) {
